@@ -11,7 +11,12 @@ Workload at every N: the configuration BASELINE.json's metric is quoted on — a
 GPU (weak scaling: the global grid has N * 1e6 rows), d = 20, n_train = 512, Matérn-5/2 ARD,
 fixed-theta mode (prior modes of the BAYBE preset), qLogEI, fp64.
 
+A plain run sets up, warms up, times --steps steps and prints the result line; ``--full`` adds everything else this file
+measures (device fit, greedy batch, end-to-end recommend(), per-kernel timings and roofline, the other scaling mode for N > 1, CPU
+baselines).  ``--dump-outputs DIR`` writes what the last timed step computed as DIR/<name>.npy (fp64).
+
   python bench.py                       # 1 GPU, the metric's own configuration (BASELINE configs[2], one GPU's shard)
+  python bench.py --full                # the same, with every figure beyond the headline
   python bench.py --config cfg2|cfg4|cfg5   # the other BASELINE configurations, each with its own roofline record (cfg2 / cfg5 also
                                         #   with --gpus N: row shards like the default):
                                         #   cfg2 = configs[1] 1e5 x 15, n = 256;  cfg4 = configs[3] ICM over 4 tasks, 1e5 x (15 + task),
@@ -38,6 +43,26 @@ import numpy as np  # noqa: E402
 
 FP64_MFMA_PEAK_TFLOPS = 78.6  # AMD MI355X datasheet: FP64 matrix = FP64 vector = 78.6 TFLOP/s
 TOPK = 8
+DUMP_ROWS = 1 << 20  # --dump-outputs: per-row arrays beyond this many rows are a fixed sample (at most 4 files x 8 MB)
+
+
+def dump_outputs(out_dir, vals, idx, per_row):
+    """``--dump-outputs``: the last timed step's top-k (values, global row numbers) and its per-row device arrays (``per_row``:
+    name -> fp64 device tensor of the rank's rows) as ``<name>.npy`` in fp64; beyond DUMP_ROWS rows a seeded sample of the rows,
+    the same rows every run, whose numbers go to ``sample_rows.npy``."""
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    np.save(out / "topk_values.npy", np.asarray(vals, dtype=np.float64).ravel())
+    np.save(out / "topk_indices.npy", np.asarray(idx, dtype=np.float64).ravel())
+    rows = None
+    for name, t in per_row.items():
+        a = t.detach().cpu().numpy().astype(np.float64, copy=False)
+        if len(a) > DUMP_ROWS:
+            if rows is None:
+                rows = np.sort(np.random.default_rng(0).choice(len(a), DUMP_ROWS, replace=False))
+                np.save(out / "sample_rows.npy", rows.astype(np.float64))
+            a = a[rows]
+        np.save(out / f"{name}.npy", a)
 
 
 def synth_problem(rows: int, d: int, n: int, rank: int):
@@ -219,6 +244,12 @@ def parse_args(argv=None):
                                                           "than one GPU: BASELINE configs[2] is ONE 1e6-row grid row-sharded)")
     ap.add_argument("--weak", action="store_true", help="--rows rows PER GPU (weak scaling; for more than one GPU the headline is "
                                                         "otherwise the strong-scaled grid and the weak figure sits in extra)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (fp64; rank 0's rows, a fixed sample beyond "
+                         f"{DUMP_ROWS} rows)")
+    ap.add_argument("--full", action="store_true", help="measure everything beyond the headline figure (the options below this one "
+                                                        "take effect with it): fit, greedy batch, end-to-end recommend(), per-kernel "
+                                                        "timings and roofline, the other scaling mode, CPU baselines")
     ap.add_argument("--cpu-budget", type=float, default=15.0, help="seconds of CPU baseline work (0 = skip)")
     ap.add_argument("--fit", nargs="?", type=int, const=1, default=-1,
                     help="time a device hyper-parameter fit outside the timed region (extra.fit_ms); default: on for single-task "
@@ -337,7 +368,7 @@ def run(args):
             g = engine.HipGP(local_rank)
             g.set_model(spec, Xt, yo)
             engines.append(g)
-        if args.fit == 1 or (args.fit < 0 and world == 1):  # the three targets' fits, one host thread and one stream each (CompositeSurrogate)
+        if args.full and (args.fit == 1 or (args.fit < 0 and world == 1)):  # the three targets' fits, one host thread and one stream each (CompositeSurrogate)
             for _ in range(2):  # (what HipCompositeImpl.fit does: engine.fit_side_by_side - a private stream per fit)
                 t0 = time.perf_counter()
                 fis = engine.fit_side_by_side([g.fit for g in engines], device=local_rank)
@@ -359,22 +390,23 @@ def run(args):
         extra["nehvi_first_setup_ms"] = (time.perf_counter() - t0) * 1e3  # (also pays the first allocations of the extended models)
         extra["nehvi_prune_ms"] = nehvi.last_setup_ms.get("prune")
         extra["nehvi_prune_parts_ms"] = {k: round(v, 3) for k, v in getattr(nehvi, "last_prune_ms", {}).items()}
-        ts_setup = []
-        for _ in range(5):  # the per-selection-step set-up: extended models, baseline samples, box decompositions (device)
-            t0 = time.perf_counter()
-            nehvi.prepare(1234, prune_seed=4321)
+        if args.full:
+            ts_setup = []
+            for _ in range(5):  # the per-selection-step set-up: extended models, baseline samples, box decompositions (device)
+                t0 = time.perf_counter()
+                nehvi.prepare(1234, prune_seed=4321)
+                torch.cuda.synchronize()
+                ts_setup.append((time.perf_counter() - t0) * 1e3)
+            extra["nehvi_setup_ms"] = float(np.median(ts_setup))
+            # pruning as every later recommend() pays it (the acquisition function is rebuilt per call, acqfs.py:477-484): a second
+            # object's first prepare - without the process's one-off costs (self-check of the native generator, the engine's direction numbers)
+            nehvi2 = HipNEHVI(engines, np.ones(len(ys)), Xt, ref, n_mc_samples=S, prune_baseline=True, device=local_rank)
             torch.cuda.synchronize()
-            ts_setup.append((time.perf_counter() - t0) * 1e3)
-        extra["nehvi_setup_ms"] = float(np.median(ts_setup))
-        # pruning as every later recommend() pays it (the acquisition function is rebuilt per call, acqfs.py:477-484): a second object's
-        # first prepare - without the process's one-off costs (self-check of the native generator, the engine's direction numbers)
-        nehvi2 = HipNEHVI(engines, np.ones(len(ys)), Xt, ref, n_mc_samples=S, prune_baseline=True, device=local_rank)
-        torch.cuda.synchronize()
-        nehvi2.prepare(1234, prune_seed=4321)
-        torch.cuda.synchronize()
-        extra["nehvi_prune_ms_steady"] = nehvi2.last_setup_ms.get("prune")
-        extra["nehvi_prune_parts_ms_steady"] = {k: round(v, 3) for k, v in getattr(nehvi2, "last_prune_ms", {}).items()}
-        del nehvi2
+            nehvi2.prepare(1234, prune_seed=4321)
+            torch.cuda.synchronize()
+            extra["nehvi_prune_ms_steady"] = nehvi2.last_setup_ms.get("prune")
+            extra["nehvi_prune_parts_ms_steady"] = {k: round(v, 3) for k, v in getattr(nehvi2, "last_prune_ms", {}).items()}
+            del nehvi2
         extra["nehvi_setup_parts_ms"] = {k: round(v, 3) for k, v in nehvi.last_setup_ms.items()}
         extra["nehvi_baseline_points"] = int(len(nehvi.X_b_current))
         extra["nehvi_cells_per_sample"] = float(nehvi.n_cells) / S
@@ -384,7 +416,7 @@ def run(args):
     else:
         gp = engine.HipGP(local_rank)
         gp.set_model(spec, Xt, y)
-        if args.fit == 1 or (args.fit < 0 and world == 1):
+        if args.full and (args.fit == 1 or (args.fit < 0 and world == 1)):
             for _ in range(2 if spec.n_tasks == 1 else 1):  # (second of two fits: the first pays the allocations; the ICM fit is ~1000 evaluations)
                 t0 = time.perf_counter()
                 fi = gp.fit()
@@ -426,8 +458,9 @@ def run(args):
     def make_step(Xs, row_start):
         """One selection step over the resident rows ``Xs`` (global rows ``row_start ...``): three launches - posterior, qLogEI with
         sample slices (which leaves the chunk keys), selection - whose k results land in host-mapped memory; output buffers are the
-        step loop's own."""
+        step loop's own; ``last`` holds the per-row device arrays of the latest step (for --dump-outputs)."""
         bufs = [torch.empty(Xs.shape[0], dtype=torch.float64, device=Xs.device) for _ in range(3)]
+        last = {}
 
         def step():
             # posterior and qLogEI as two kernels: measured 1.5 % faster than the single fused posterior+qLogEI kernel
@@ -435,6 +468,7 @@ def run(args):
             # either way, but a separate launch runs it at full occupancy and leaves the fused kernel's LDS to the kernel-value cache
             if nehvi is not None:  # extended-model variance pass + S conditional means per target, then the cell kernel
                 scores = nehvi.score(Xs)
+                last["acquisition_scores"] = scores
                 if shard is None:
                     return gp.topk(scores, TOPK)
                 if use_rccl:  # (BASELINE configs[4] is an 8-GPU configuration: row shards, the same all-gather of per-shard top-k)
@@ -446,11 +480,15 @@ def run(args):
                 _, vals, idx = gp.qlogei_topk(mean, var, z, best_f, 1.0, TOPK, scores=bufs[2])
                 return vals, idx
             scores = gp.qlogei(mean, var, z, best_f, 1.0)
+            last["acquisition_scores"] = scores
             if use_rccl:
                 return gp.allgather_topk(scores, row_start, TOPK)
             vals, idx = gp.topk(scores, TOPK)
             return shard.global_topk(vals, idx, TOPK, device=Xs.device)
 
+        if nehvi is None:
+            last.update(posterior_mean=bufs[0], posterior_variance=bufs[1], acquisition_scores=bufs[2])
+        step.last = last
         return step
 
     step = make_step(Xd, shard.start if shard is not None else 0)
@@ -504,10 +542,11 @@ def run(args):
                 acc[fam][1] += cnt
         return acc
 
-    # Timed region: HIP events bracket the dominant kernel only.  An event between two back-to-back kernels costs the stream ~5 us
-    # (rocprofv3 trace: 10 us gaps posterior -> qLogEI -> selection with every family's events on, none without), which is 3 % of a
-    # 0.65 ms step; the other families are timed in K more steps below.
-    timers(True, (DOM,))
+    # Timed region: with --full, HIP events bracket the dominant kernel only.  An event between two back-to-back kernels costs the
+    # stream ~5 us (rocprofv3 trace: 10 us gaps posterior -> qLogEI -> selection with every family's events on, none without), which is
+    # 3 % of a 0.65 ms step; the other families are timed in K more steps below.  A plain run has no events in it.
+    if args.full:
+        timers(True, (DOM,))
     fence()
     step_ms = []
     t0 = time.perf_counter()
@@ -517,34 +556,37 @@ def run(args):
         step_ms.append((time.perf_counter() - ts) * 1e3)
     fence()
     dt = time.perf_counter() - t0
-    dom_timed = read_timers()[DOM]
-    # Instrumented steps: every family's events (and, for qLogNEHVI, the targets' passes one after the other instead of overlapped on
-    # their own streams - HIP-event times of one family would otherwise include the others' work).
-    seq = nehvi is not None and getattr(nehvi, "concurrent", False) and nehvi.m > 1
-    if seq:
-        nehvi.concurrent = False
-    timers(True)
-    step()
-    read_timers()
-    fence()
-    t_ins = time.perf_counter()
-    for _ in range(args.steps):
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, vals, idx, step.last)
+    if args.full:
+        dom_timed = read_timers()[DOM]
+        # Instrumented steps: every family's events (and, for qLogNEHVI, the targets' passes one after the other instead of overlapped
+        # on their own streams - HIP-event times of one family would otherwise include the others' work).
+        seq = nehvi is not None and getattr(nehvi, "concurrent", False) and nehvi.m > 1
+        if seq:
+            nehvi.concurrent = False
+        timers(True)
         step()
-    fence()
-    extra["ms_per_step_instrumented"] = (time.perf_counter() - t_ins) / args.steps * 1e3
-    fam_step = read_timers()
-    fam_step[DOM] = dom_timed
-    timers(False)
-    if seq:
-        nehvi.concurrent = True
-    extra["device_ms_note"] = (f"'{DOM}': HIP events over the timed region (the only events in it); the other families: HIP events over "
-                               f"{args.steps} further steps with every family instrumented"
-                               + (", the targets' passes in sequence" if seq else ""))
-    fused_ms, fused_launches = fam_step["posterior"]
+        read_timers()
+        fence()
+        t_ins = time.perf_counter()
+        for _ in range(args.steps):
+            step()
+        fence()
+        extra["ms_per_step_instrumented"] = (time.perf_counter() - t_ins) / args.steps * 1e3
+        fam_step = read_timers()
+        fam_step[DOM] = dom_timed
+        timers(False)
+        if seq:
+            nehvi.concurrent = True
+        extra["device_ms_note"] = (f"'{DOM}': HIP events over the timed region (the only events in it); the other families: HIP events "
+                                   f"over {args.steps} further steps with every family instrumented"
+                                   + (", the targets' passes in sequence" if seq else ""))
+        fused_ms, fused_launches = fam_step["posterior"]
+        extra["device_ms_per_step"] = {fam: v[0] / args.steps for fam, v in fam_step.items() if v[1]}
     extra["top_indices"] = [int(i) for i in np.asarray(idx).ravel()[:TOPK]]  # the last step's top-k (global row numbers)
     extra["ms_per_step_median"] = float(np.median(step_ms))
     extra["ms_per_step_mean"] = float(np.mean(step_ms))
-    extra["device_ms_per_step"] = {fam: v[0] / args.steps for fam, v in fam_step.items() if v[1]}
     form = timed_engines[0].posterior_kernel_form()
     if dist_on:
         tt = torch.tensor([dt], dtype=torch.float64, device="cpu" if single_dev else "cuda")
@@ -557,7 +599,7 @@ def run(args):
     value = total_rows * args.steps / dt
 
     # ---- extra (qLogNEHVI): what a selection step costs WITH its set-up, and a greedy batch ------------------------------------
-    if nehvi is not None:
+    if args.full and nehvi is not None:
         def selection_step():
             nehvi.prepare(1234, prune_seed=4321)
             return step()
@@ -589,7 +631,7 @@ def run(args):
     # ---- extra: the OTHER scaling mode of the same configuration next to the headline (N > 1 only) ----------------------------------
     # headline strong (default for N > 1: the configuration's grid split over the ranks) -> extra.weak_cfg3: a full grid per rank;
     # headline weak (--weak) -> extra.strong_cfg3: BASELINE configs[2]'s 1e6 rows split over the ranks
-    if dist_on and cfg == "cfg3" and nehvi is None and (world > 1 or not args.strong):
+    if args.full and dist_on and cfg == "cfg3" and nehvi is None and (world > 1 or not args.strong):
         other_strong = not args.strong
         g_rows = CONFIGS["cfg3"][0]
         if other_strong:
@@ -624,7 +666,7 @@ def run(args):
 
     # ---- extra: one greedy batch (optimize_acqf_discrete, q = --greedy) on the same shard, timed per kernel family ----
     pending_roofline = None
-    if args.greedy > 1 and nehvi is None:
+    if args.full and args.greedy > 1 and nehvi is None:
         gp.timing(True)
         for fam in ("posterior", "cross", "pending"):
             gp.timing_read(reset=True, family=fam)
@@ -665,7 +707,7 @@ def run(args):
             }
 
     # ---- extra: end-to-end recommend() through the plug-in surface ("report additionally ... end-to-end recommend()") ----
-    if (args.e2e == 1 or (args.e2e < 0 and world == 1)) and not dist_on:
+    if args.full and (args.e2e == 1 or (args.e2e < 0 and world == 1)) and not dist_on:
         q_e2e = args.greedy if args.greedy > 0 else 5
         if nehvi is not None:  # configs[4]: three fits + baseline pruning + the greedy batch, per call
             from baybe_amd.acquisition import qLogNoisyExpectedHypervolumeImprovement
@@ -688,7 +730,9 @@ def run(args):
 
     kernel_names = {"cooperative": "bbh_coop_posterior_kernel", "windowed": "bbh_fused_posterior_kernel",
                     "cooperative-2sweep": "bbh_coop2_posterior_kernel"}
-    if nehvi is None:
+    if not args.full:
+        roofline = None
+    elif nehvi is None:
         flops_per_cand = n * n + 2 * n * d + 16 * n + 16 * S
         avg_ms = fused_ms / max(fused_launches, 1)
         achieved = rows_local * flops_per_cand / (avg_ms * 1e-3) / 1e12 if avg_ms > 0 else 0.0
@@ -799,9 +843,9 @@ def run(args):
                         f"qLogEI S={S}, fixed-theta, top-{TOPK} to host (BASELINE configs[3])",
                 "cfg5": (f"{total_rows} x {d} discrete grid row-sharded over {world} GPUs ({rows_local} rows on rank 0)" if (args.strong and world > 1)
                          else f"{rows_local} x {d} discrete grid") + f", ParetoObjective of 3 targets -> qLogNEHVI, n_train={n}, S={S} MC samples, "
-                        f"pruned baseline, top-{TOPK} to host (BASELINE configs[4], one GPU's share); the timed step is the SCORING PASS - a "
-                        f"selection step adds {extra.get('nehvi_setup_ms', float('nan')):.2f} ms of set-up: extra.ms_per_selection_step = "
-                        f"{extra.get('ms_per_selection_step', float('nan')):.2f} ms",
+                        f"pruned baseline, top-{TOPK} to host (BASELINE configs[4], one GPU's share); the timed step is the SCORING PASS"
+                        + (f" - a selection step adds {extra.get('nehvi_setup_ms', float('nan')):.2f} ms of set-up: "
+                           f"extra.ms_per_selection_step = {extra.get('ms_per_selection_step', float('nan')):.2f} ms" if args.full else ""),
             }[cfg],
             "baseline_config": cfg,
             "global_rows": total_rows,
@@ -811,10 +855,12 @@ def run(args):
         "roofline": roofline,
         "extra": extra,
     }
+    if roofline is None:  # (a plain run times no kernel on its own)
+        del out["roofline"]
     if pending_roofline is not None:
         out["extra"]["roofline_pending_kernels"] = pending_roofline
 
-    if rank == 0 and world == 1 and args.cpu_budget > 0 and cfg in ("cfg3", "cfg2"):
+    if args.full and rank == 0 and world == 1 and args.cpu_budget > 0 and cfg in ("cfg3", "cfg2"):
         from oracle import cpu_baseline as cb
         from oracle import gp_oracle as go
 
@@ -845,7 +891,7 @@ def run(args):
             "default_threads": default_threads,
         }
         out["extra"]["speedup_vs_cpu_baseline"] = value / cps
-    if rank == 0 and world == 1 and args.cpu_budget > 0 and fit_start_raw is not None:
+    if args.full and rank == 0 and world == 1 and args.cpu_budget > 0 and fit_start_raw is not None:
         # the fit objective on the host cores beside the device fit: evaluations of the oracle's objective (torch-CPU fp64, autograd
         # gradient - what fit_gpytorch_mll evaluates per L-BFGS-B step) at the fit's starting point, a bounded sample
         import torch as _t

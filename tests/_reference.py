@@ -21,7 +21,10 @@ _STUBS = Path(__file__).resolve().parent / "_stubs"
 
 
 def reference_available() -> bool:
-    return (REFERENCE_ROOT / "baybe" / "__init__.py").exists()
+    try:  # (a tree the user may not enter counts as absent: Path.exists lets PermissionError through)
+        return (REFERENCE_ROOT / "baybe" / "__init__.py").is_file()
+    except OSError:
+        return False
 
 
 def reference_baybe():

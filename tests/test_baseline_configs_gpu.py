@@ -106,13 +106,40 @@ def test_bench_greedy_indices_equal_the_full_set_golden():
     import sys
 
     root = Path(__file__).resolve().parents[1]
-    out = subprocess.run([sys.executable, str(root / "bench.py"), "--steps", "2", "--warmup", "1", "--cpu-budget", "0"],
+    out = subprocess.run([sys.executable, str(root / "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--cpu-budget", "0"],
                          capture_output=True, text=True, timeout=600, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads(out.stdout.strip().splitlines()[-1])
     g = np.load(GOLD / "cfg3_full_ranking.npz")
     assert line["extra"]["greedy_q5_indices"] == g["greedy_idx"].tolist()
     assert line["config"]["workload"].startswith("1000000 x 20") and line["roofline"]["frac"] > 0.5
+
+
+def test_plain_bench_dumps_what_its_last_step_computed(tmp_path):
+    """A plain ``bench.py`` run (no ``--full``) times only the headline steps and, with ``--dump-outputs``, writes the last timed
+    step's arrays: its top-8, posterior mean / variance and qLogEI scores of all 1e6 rows - the oracle's values of
+    tests/golden/cfg3_full_ranking.npz."""
+    import json
+    import subprocess
+    import sys
+
+    root = Path(__file__).resolve().parents[1]
+    out = subprocess.run([sys.executable, str(root / "bench.py"), "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)],
+                         capture_output=True, text=True, timeout=600, cwd=root)
+    assert out.returncode == 0, out.stderr[-2000:]
+    line = json.loads(out.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["unit"] == "candidates/s" and "roofline" not in line
+    assert "fit_ms" not in line["extra"] and "cpu_baseline" not in line
+    dump = {p.stem: np.load(p) for p in tmp_path.glob("*.npy")}
+    assert set(dump) == {"topk_values", "topk_indices", "posterior_mean", "posterior_variance", "acquisition_scores"}
+    assert all(a.dtype == np.float64 for a in dump.values()) and len(dump["acquisition_scores"]) == 1_000_000
+    g = np.load(GOLD / "cfg3_full_ranking.npz")
+    assert dump["topk_indices"].astype(np.int64).tolist() == g["top_idx"][:8].tolist() == line["extra"]["top_indices"]
+    assert np.allclose(dump["topk_values"], g["top_val"][:8], rtol=0, atol=1e-8)
+    assert np.allclose(dump["acquisition_scores"][::256], g["sample_scores"], rtol=0, atol=1e-8)
+    rows = g["post_rows"]
+    assert np.allclose(dump["posterior_mean"][rows], g["post_mean"], rtol=1e-9, atol=1e-12)
+    assert np.allclose(dump["posterior_variance"][rows], g["post_var"], rtol=1e-8)
 
 
 # ---- fit parity at size (VERDICT r2: it stopped at n = 128): the device's whole L-BFGS-B run against the oracle's ----------

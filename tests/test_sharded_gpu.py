@@ -191,7 +191,7 @@ def test_bench_starts_its_own_ranks_and_reports_one_json_line():
     root = Path(__file__).resolve().parent.parent
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env["BENCH_SINGLE_DEVICE"] = "1"
-    cmd = [sys.executable, str(root / "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--rows", "150000",
+    cmd = [sys.executable, str(root / "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--rows", "150000",
            "--cpu-budget", "0", "--greedy", "3"]
     out = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -220,7 +220,7 @@ def test_bench_under_torchrun_as_the_driver_launches_it():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "MASTER_ADDR")}
     env["BENCH_SINGLE_DEVICE"] = "1"
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), str(root / "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
+           "--master-port", str(_free_port()), str(root / "bench.py"), "--full", "--gpus", "2", "--steps", "3", "--warmup", "1",
            "--cpu-budget", "0", "--greedy", "0"]  # (default rows: rank 0's grid and training rows are the single-process ones)
     out = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
@@ -281,7 +281,7 @@ def test_bench_sharded_path_over_rccl_with_one_rank(collective):
 
     root = Path(__file__).resolve().parent.parent
     base = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "BENCH_SINGLE_DEVICE")}
-    cmd = [sys.executable, str(root / "bench.py"), "--steps", "2", "--warmup", "1", "--rows", "120000", "--cpu-budget", "0",
+    cmd = [sys.executable, str(root / "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--rows", "120000", "--cpu-budget", "0",
            "--greedy", "3"]
     recs = []
     for env in (dict(base), dict(base, BENCH_FORCE_COLLECTIVE="1", BBH_COLLECTIVE=collective, MASTER_PORT=str(_free_port()))):
