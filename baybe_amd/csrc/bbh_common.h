@@ -297,6 +297,7 @@ struct bbh_handle {
   int64_t rstream_frags = 0;
   int coop_g0 = 0;
   int last_form = -1;             // bbh_last_posterior_form
+  int last_fit_form = -1;         // bbh_last_fit_form (enum bbh_fit_form)
   int64_t nb_ext = 0;             // blocks incl. pending points (mean/cross pass)
   // pending state
   int p = 0;
@@ -339,6 +340,8 @@ struct bbh_handle {
   bool tile_d_sc1 = false;        // env BBH_TILE_ACQ=0: row heads take D_{I-1} through sc1 loads without an acquire fence (valid after write-through stores; measured: no gain, so the fence form stays the default)
   bool tile_wt = true;            // env BBH_TILE_WT=0: tiles handed between workgroups through plain stores + an agent-scope release fence instead of write-through (sc1) stores (A/B)
   int tiles_did_mt = 0;           // tiles of K^-1 the last tile-dataflow launch built itself (bbh_potrf_trtri_from_inputs with mt_args; block row 0 first)
+  int tiles_mt_asked = 0;         // ... and how many it was asked for (bbh_last_fit_form: all of them or a part)
+  bool potrf_tiles_ran = false;   // the last bbh_potrf_trtri was the tile-dataflow launch (false: per-step launches)
   bool tile_mt_partial = false;   // env BBH_TILE_MT=partial
   bool tile_mt = true;            // env BBH_TILE_MT=0: K^-1's tiles stay in the dataflow tail (A/B)
   bool info_clean = false;        // the Cholesky flag on the device is known to be 0 (the dataflow tail's last role resets it)

@@ -930,6 +930,13 @@ bool bbh_fit_flow_launch(bbh_handle* h, const double* theta_dev, double* out_dev
     }
   }
   if (prepare_only) return true;
+  // The forms that factorise read the Cholesky flag as 0 on entry (their last role copies it out and resets it).  The reset at the
+  // state's creation does not cover a flag the state never saw: a fresh d_info of a model with another shape (set_model keeps the
+  // state when np and the criterion stay), or one a launch-path factorisation left non-zero - read as "not positive definite".
+  if (!tail_only && !h->info_clean && hipMemsetAsync(h->d_info, 0, sizeof(int), h->stream) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
   if (st->ticket_base > (1 << 30)) {  // cumulative counters: start over long before they wrap
     if (hipStreamSynchronize(h->stream) != hipSuccess || hipMemset(st->d_flags + FF_COUNTERS, 0, sizeof(int) * 8) != hipSuccess) {
       st->failed = true;

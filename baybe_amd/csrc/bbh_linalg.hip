@@ -551,6 +551,7 @@ static bool bbh_potrf_tiles(bbh_handle* h, const double* gram_theta = nullptr, c
     if (ntiles + ma.nM > h->tiles_per_device) ma.nM = h->tile_mt_partial ? h->tiles_per_device - ntiles : 0;
   }
   h->tiles_did_mt = ma.nM;
+  h->tiles_mt_asked = mt ? mt->nM : 0;
   const int grid_tiles = ntiles + ma.nM;
   if (h->tile_spin_limit != h->tile_spin_limit_set) {
     if (hipMemcpyToSymbol(HIP_SYMBOL(pd_spin_limit), &h->tile_spin_limit, sizeof(int)) != hipSuccess) {
@@ -835,7 +836,8 @@ extern "C" int bbh_tiles_trace_read(bbh_handle* h, long long* stamps_host, int c
 }
 
 void bbh_potrf_trtri(bbh_handle* h) {
-  if (bbh_potrf_tiles(h)) return;
+  h->potrf_tiles_ran = bbh_potrf_tiles(h);
+  if (h->potrf_tiles_ran) return;
   hipStream_t s = h->stream;
   const int64_t np = h->np, nbk = np / 64;
   hipMemsetAsync(h->d_X, 0, sizeof(double) * np * np, s);

@@ -761,14 +761,19 @@ static int bbh_fit_enqueue(bbh_handle* h) {
   hipStream_t s = h->stream;
   const int64_t np = h->np, n = h->n;
   const int64_t tl = bbh_theta_len_of(h);
-  if (bbh_is_rff(h)) return bbh_rff_fit_enqueue(h);  // the RFF kernel's model lives in feature space (bbh_rff.hip)
+  if (bbh_is_rff(h)) {  // the RFF kernel's model lives in feature space (bbh_rff.hip)
+    h->last_fit_form = BBH_FIT_FORM_RFF;
+    return bbh_rff_fit_enqueue(h);
+  }
   {  // small models: the whole evaluation in one workgroup (bbh_linalg.hip), reading theta from and writing the results to the
      // pinned staging buffers themselves - one launch, no copies
     void *th_dev = nullptr, *out_dev = nullptr, *info_dev = nullptr;
     if (h->fit_small && h->np == 64 && hipHostGetDevicePointer(&th_dev, h->pin_theta, 0) == hipSuccess &&
         hipHostGetDevicePointer(&out_dev, h->pin_out, 0) == hipSuccess && hipHostGetDevicePointer(&info_dev, h->pin_info, 0) == hipSuccess &&
-        bbh_fit_small_launch(h, 0.0, (const double*)th_dev, (double*)out_dev, (int*)info_dev))
+        bbh_fit_small_launch(h, 0.0, (const double*)th_dev, (double*)out_dev, (int*)info_dev)) {
+      h->last_fit_form = BBH_FIT_FORM_SMALL;
       return 0;
+    }
     (void)hipGetLastError();
   }
   {  // 64 < np <= 1024: the whole evaluation as one dataflow launch (bbh_fitflow.hip), the same zero-copy staging
@@ -782,8 +787,10 @@ static int bbh_fit_enqueue(bbh_handle* h) {
         hipHostGetDevicePointer(&out_dev, h->pin_out, 0) == hipSuccess && hipHostGetDevicePointer(&info_dev, h->pin_info, 0) == hipSuccess) {
       *h->pin_info = -99;  // (sentinel: the kernel's last role writes the flag; a launch that gave up never does)
       // (theta as kernel arguments when it fits: ~250 workgroups fetching it from the host-mapped buffer is the slower way)
-      if (bbh_fit_flow_launch(h, tl <= 52 ? nullptr : (const double*)th_dev, (double*)out_dev, (int*)info_dev, false, h->pin_theta, h->fit_flow == 3 && h->np <= 1024)) {
+      const bool split = h->fit_flow == 3 && h->np <= 1024;
+      if (bbh_fit_flow_launch(h, tl <= 52 ? nullptr : (const double*)th_dev, (double*)out_dev, (int*)info_dev, false, h->pin_theta, split)) {
         h->flow_in_flight = true;
+        h->last_fit_form = split ? BBH_FIT_FORM_SPLIT : BBH_FIT_FORM_ONE_LAUNCH;
         return 0;
       }
     }
@@ -815,6 +822,8 @@ static int bbh_fit_enqueue(bbh_handle* h) {
         *h->pin_info = -99;
         if (bbh_fit_flow_launch(h, th_src, (double*)out_dev, (int*)info_dev, true, h->pin_theta, false, h->tiles_did_mt)) {
           h->flow_in_flight = true;
+          h->last_fit_form = h->tiles_did_mt == 0 ? BBH_FIT_FORM_TILES
+                             : (h->tiles_did_mt < h->tiles_mt_asked ? BBH_FIT_FORM_TILES_MT_PARTIAL : BBH_FIT_FORM_TILES_MT);
           return 0;
         }
         (void)hipGetLastError();  // (the tail is unavailable: the evaluation starts over below, launch by launch)
@@ -839,6 +848,7 @@ static int bbh_fit_enqueue(bbh_handle* h) {
       *h->pin_info = -99;
       if (bbh_fit_flow_launch(h, h->d_theta, (double*)out_dev, (int*)info_dev, true)) {
         h->flow_in_flight = true;
+        h->last_fit_form = h->potrf_tiles_ran ? BBH_FIT_FORM_GRAM_TILES : BBH_FIT_FORM_STEPS_TAIL;
         return 0;
       }
       (void)hipGetLastError();  // (resources: the handle has stopped using the form; this evaluation starts over on the launch path)
@@ -846,6 +856,7 @@ static int bbh_fit_enqueue(bbh_handle* h) {
     int rc0 = bbh_chol_and_alpha(h, 0.0, nullptr);
     if (rc0) return rc0;
   }
+  h->last_fit_form = BBH_FIT_FORM_LAUNCH;
   int rc = 0;
   // M = X^T X.  One 64 x 64 output tile per workgroup means np / 64 squared workgroups walking all of K: 35 us at np = 512
   // on a quarter of the CUs.  Up to np = 1024 the product is split four ways along K (batched launch into four partial

@@ -987,6 +987,12 @@ class HipGP:
         return {0: "windowed", 1: "cooperative", 2: "materialised", 3: "cooperative-2sweep", 4: "cooperative-generic",
                 5: "register-resident", 6: "feature-space"}.get(self._lib.bbh_last_posterior_form(self._h), "none")
 
+    def fit_evaluation_form(self) -> str:
+        """Which path the last fit evaluation (``data_term``, every objective call of ``fit``) ran as - after a give-up of a dataflow
+        launch, the path that produced the returned numbers (``enum bbh_fit_form`` in include/baybe_hip.h)."""
+        return {0: "launch", 1: "small", 2: "tiles+mt", 3: "tiles+mt-partial", 4: "tiles", 5: "gram+tiles", 6: "one-launch",
+                7: "split", 8: "rff", 9: "steps+tail"}.get(self._lib.bbh_last_fit_form(self._h), "none")
+
     def timing(self, enable, families=None):
         """HIP-event timing of the kernel families on / off; ``families`` (names as for ``timing_read``) restricts the events to those
         families - an event between two back-to-back kernels costs the stream ~5 us."""

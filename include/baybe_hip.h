@@ -411,6 +411,21 @@ int bbh_timing_read(bbh_handle* h, double* fused_ms_total, int64_t* fused_launch
  * Polynomial, Periodic: bbh_coopg_posterior_kernel), 5 = register- / LDS-resident (n <= 128, bbh_small_posterior_kernel),
  * 6 = feature space (BBH_KERNEL_RFF: bbh_rff_posterior_kernel), -1 = none yet. */
 int bbh_last_posterior_form(bbh_handle* h);
+/* Form the last fit evaluation (bbh_fit_value_grad) of this handle ran as, i.e. the path that produced the returned value and gradient
+ * (after a give-up of a dataflow launch: the path that redid the evaluation), -1 = none yet. */
+enum bbh_fit_form {
+  BBH_FIT_FORM_LAUNCH = 0,           /* launch by launch: factorisation, K^-1, value and gradient kernels (bbh_chol_and_alpha + ...) */
+  BBH_FIT_FORM_SMALL = 1,            /* np = 64: one workgroup (bbh_fit_small_kernel) */
+  BBH_FIT_FORM_TILES_MT = 2,         /* tile-dataflow factorisation building its Gram tiles and all of K^-1's tiles, then the dataflow tail */
+  BBH_FIT_FORM_TILES_MT_PARTIAL = 3, /* ... building a part of K^-1's tiles (BBH_TILE_MT=partial beyond co-residency) */
+  BBH_FIT_FORM_TILES = 4,            /* ... building its Gram tiles only */
+  BBH_FIT_FORM_GRAM_TILES = 5,       /* Gram launch, tile-dataflow factorisation, dataflow tail */
+  BBH_FIT_FORM_ONE_LAUNCH = 6,       /* the whole evaluation as one dataflow launch (bbh_fit_flow_kernel) */
+  BBH_FIT_FORM_SPLIT = 7,            /* two dataflow launches: factorisation + K^-1, then the rest (BBH_FIT_FLOW=3) */
+  BBH_FIT_FORM_RFF = 8,              /* feature-space evaluation of a BBH_KERNEL_RFF model */
+  BBH_FIT_FORM_STEPS_TAIL = 9        /* Gram launch, per-step factorisation launches, dataflow tail */
+};
+int bbh_last_fit_form(bbh_handle* h);
 enum bbh_timed_family {
   BBH_TIMED_POSTERIOR = 0, BBH_TIMED_CROSS = 1, BBH_TIMED_PENDING = 2,
   BBH_TIMED_COLUMNS = 3,  /* bbh_posterior_columns: conditional means under S target columns (qLogNEHVI) */
