@@ -617,7 +617,7 @@ extern "C" int bbh_qlogei_q1(bbh_handle* h, const double* mean_dev, const double
   }
   if (N == 0) return 0;
   BBH_HIP_TRY(h, hipSetDevice(h->device));
-  if (h->q1_sliced) {  // sample-sliced form (bbh_select.hip); 1 = does not apply (S beyond its LDS tables)
+  if (h->sw.q1_sliced) {  // sample-sliced form (bbh_select.hip); 1 = does not apply (S beyond its LDS tables)
     const int rc = bbh_qlogei_q1_sliced(h, mean_dev, var_dev, N, z_host, S, best_f, sign, alive_dev, scores_dev);
     if (rc <= 0) return rc;
   }
@@ -679,9 +679,9 @@ static int bbh_qlogei_pending_impl(bbh_handle* h, const double* mean_dev, const 
   // sample slices for small candidate sets (~16 waves per SIMD; linear-domain form; each slice at least 32 samples)
   int slices = 1;
 #if BBH_PENDING_FAST && !BBH_PENDING_LSE
-  if (fits && !h->pending_lds_form && p + 1 <= 14) {
+  if (fits && !h->sw.pending_lds_form && p + 1 <= 14) {
     int64_t want = ((int64_t)16 * 4 * h->num_cu * 64) / (h->slice_rows > 0 ? h->slice_rows : N);
-    if (const char* e = getenv("BBH_PENDING_SLICES")) want = atoi(e);
+    if (h->sw.pending_slices != INT_MIN) want = h->sw.pending_slices;
     if (want > S / 32) want = S / 32;
     slices = (int)(want < 1 ? 1 : (want > 32 ? 32 : want));
     if (slices > 1) {
@@ -696,7 +696,7 @@ static int bbh_qlogei_pending_impl(bbh_handle* h, const double* mean_dev, const 
     bbh_launch_pending_q<QV>(h->stream, mean_dev, var_dev, cross_dev, N, dmp, dcpp, dz, (int)S, best_f, sign,    \
                              alive_dev, scores_dev, slices, h->d_ws);                                            \
     break;
-  switch (fits && !h->pending_lds_form ? p + 1 : 0) {
+  switch (fits && !h->sw.pending_lds_form ? p + 1 : 0) {
     BBH_PENDING_Q(2)
     BBH_PENDING_Q(3)
     BBH_PENDING_Q(4)
@@ -832,8 +832,7 @@ extern "C" int bbh_qlogei_pending_big(bbh_handle* h, const double* mean_dev, con
   // chunks whose workspace stays below QBIG_WS_BYTES (the handle's grow-only workspace outlives the call, also in the handle pool);
   // chunks are multiples of 64 rows, every chunk addresses its own rows from 0.
   const int64_t tri_q = q * (q + 1) / 2;
-  size_t ws_bound = QBIG_WS_BYTES;
-  if (const char* e = getenv("BBH_QBIG_WS_MB")) ws_bound = (size_t)std::max(1LL, atoll(e)) << 20;
+  const size_t ws_bound = h->sw.qbig_ws_mb ? (size_t)h->sw.qbig_ws_mb << 20 : QBIG_WS_BYTES;
   int64_t chunk = (int64_t)(ws_bound / (sizeof(double) * (size_t)tri_q)) / 64 * 64;
   if (chunk < 64) chunk = 64;
   if (chunk > N) chunk = N;
@@ -1320,21 +1319,19 @@ static int bbh_qlognehvi_run(bbh_handle* h, NehviArgs& a, const double* len_dev)
   const int64_t N = a.N, S = a.S;
   dim3 grid((unsigned)((N + 255) / 256)), block(256);
   bbh_timed_scope timed(h, BBH_TIMED_NEHVI);
-  const char* env_log = getenv("BBH_NEHVI_LOG");
-  if (!(env_log && env_log[0] == '1')) {  // linear-domain sums (default)
+  if (!h->sw.nehvi_log) {  // linear-domain sums (default)
     const double* len = len_dev;
     // sample slices: ~16 waves per SIMD (4 SIMDs per CU; 11.3 / 10.4 / 10.0 / 9.8 ms for 6 / 12 / 24 / 48 slices at 1e5 candidates), each slice at least 8 samples
     const int64_t srows = h->slice_rows > 0 ? h->slice_rows : N;
     int64_t slices = ((int64_t)16 * 4 * h->num_cu * 64 + srows - 1) / srows;
-    if (const char* e = getenv("BBH_NEHVI_SLICES")) slices = atoi(e);
+    if (h->sw.nehvi_slices != INT_MIN) slices = h->sw.nehvi_slices;
     if (slices > S / 8) slices = S / 8;
     if (slices > 64) slices = 64;
     if (slices < 1) slices = 1;
     int rc = bbh_ensure_ws(h, sizeof(double) * (size_t)slices * (size_t)N);
     if (rc) return rc;
     dim3 sgrid(grid.x, (unsigned)slices);
-    const char* env_pk = getenv("BBH_NEHVI_PK");
-    if (env_pk && env_pk[0] == '0') {
+    if (!h->sw.nehvi_pk) {
       switch (m) {
         case 1: hipLaunchKernelGGL((bbh_qlognehvi_lin_kernel<1, false>), sgrid, block, 0, h->stream, a, len, h->d_ws); break;
         case 2: hipLaunchKernelGGL((bbh_qlognehvi_lin_kernel<2, false>), sgrid, block, 0, h->stream, a, len, h->d_ws); break;
@@ -1834,7 +1831,7 @@ extern "C" int bbh_mc_acq_pending(bbh_handle* h, int32_t kind, const double* mea
     bbh_launch_mc_pending_q<QV>(h->stream, kind, mean_dev, var_dev, cross_dev, N, dmp, dcpp, dz, dzb, (int)S,    \
                                 best_f, sign, cu, alive_dev, scores_dev);                                        \
     break;
-  switch (fits && !h->pending_lds_form ? q : 0) {
+  switch (fits && !h->sw.pending_lds_form ? q : 0) {
     BBH_MC_PENDING_Q(2)
     BBH_MC_PENDING_Q(3)
     BBH_MC_PENDING_Q(4)

@@ -4,11 +4,103 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
+#include <map>
+#include <mutex>
+
 #include "bbh_common.h"
 
 static const char* kNoHandle = "bbh: null handle";
 
 extern "C" int bbh_version(void) { return 100; }
+
+// Every run-time switch of the library, read from the environment when a handle is created (the handle pool of engine.py keys its
+// handles by the BBH_* environment for that reason).  One row per switch and member; KERNELS.md section 4.5 documents the same names.
+static bbh_switches bbh_read_switches() {
+  enum how { NOT, IS, SET, INT, MB };  // value[0] != c | value[0] == c | variable present | atoi(value) | atoll(value) clamped to [1, INT_MAX]
+  typedef bbh_switches S;
+  static const struct {
+    const char* name;
+    how parse;
+    char c;
+    bool S::*flag;
+    int S::*num;
+  } table[] = {
+      {"BBH_PIPELINE", NOT, '0', &S::use_pipeline, nullptr},
+      {"BBH_MEAN_VALU", NOT, '0', &S::use_mean_valu, nullptr},
+      {"BBH_KVCACHE", NOT, '0', &S::use_kvcache, nullptr},
+      {"BBH_KV_GLOBAL", NOT, '0', nullptr, &S::kv_global_mode},
+      {"BBH_KV_LDS", INT, 0, nullptr, &S::kv_lds_blocks},
+      {"BBH_COOP", INT, 0, nullptr, &S::coop_mode},
+      {"BBH_COOP_SMALL", NOT, '0', &S::coop_small, nullptr},
+      {"BBH_COOPG_CROSS", NOT, '0', &S::coopg_cross_on, nullptr},
+      {"BBH_SMALL", NOT, '0', &S::small_on, nullptr},
+      {"BBH_SMALL_FORCE", IS, '1', &S::small_force, nullptr},
+      {"BBH_COLUMNS_COOP", NOT, '0', &S::columns_coop, nullptr},
+      {"BBH_COLUMNS_NT", INT, 0, nullptr, &S::columns_nt},
+      {"BBH_PENDING_LDS", NOT, '0', &S::pending_lds_form, nullptr},
+      {"BBH_PENDING_SLICES", INT, 0, nullptr, &S::pending_slices},
+      {"BBH_QBIG_WS_MB", MB, 0, nullptr, &S::qbig_ws_mb},
+      {"BBH_Q1_SLICED", NOT, '0', &S::q1_sliced, nullptr},
+      {"BBH_NEHVI_LOG", IS, '1', &S::nehvi_log, nullptr},
+      {"BBH_NEHVI_SLICES", INT, 0, nullptr, &S::nehvi_slices},
+      {"BBH_NEHVI_PK", NOT, '0', &S::nehvi_pk, nullptr},
+      {"BBH_SELECT", NOT, '0', &S::select_on, nullptr},
+      {"BBH_SELECT_MAPPED", NOT, '0', &S::select_mapped, nullptr},
+      {"BBH_FIT_GRAPH", NOT, '0', &S::fit_graph_mode, nullptr},
+      {"BBH_FIT_OVERLAP", NOT, '0', &S::fit_overlap, nullptr},
+      {"BBH_FIT_SMALL", NOT, '0', &S::fit_small, nullptr},
+      {"BBH_FIT_FLOW", INT, 0, nullptr, &S::fit_flow},
+      {"BBH_FLOW_SPIN", INT, 0, nullptr, &S::flow_spin_limit},
+      {"BBH_FIT_POST1", NOT, '0', &S::fit_post1, nullptr},
+      {"BBH_FIT_TAIL1", NOT, '0', &S::fit_tail1, nullptr},
+      {"BBH_POTRF_TILES", NOT, '0', &S::potrf_tiles, nullptr},
+      {"BBH_POTRF_REG", NOT, '0', &S::potrf_register_form, nullptr},
+      {"BBH_TILE_SPIN", INT, 0, nullptr, &S::tile_spin_limit},
+      {"BBH_TILE_ACQ", IS, '0', &S::tile_d_sc1, nullptr},  // (default: acquire fence)
+      {"BBH_TILE_WT", NOT, '0', &S::tile_wt, nullptr},
+      {"BBH_TILE_MT", NOT, '0', &S::tile_mt, nullptr},
+      {"BBH_TILE_MT", IS, 'p', &S::tile_mt_partial, nullptr},
+      {"BBH_TILE_GRAM", NOT, '0', &S::tile_gram, nullptr},
+      {"BBH_TILE_GRAM_THETA", IS, 'c', &S::tile_gram_theta_copy, nullptr},
+      {"BBH_SETMODEL_UPLOAD", IS, 'c', &S::setmodel_upload_copy, nullptr},
+      {"BBH_SETMODEL_SYNC", NOT, '0', &S::setmodel_sync, nullptr},
+      {"BBH_SETMODEL_SYNC", IS, 'p', &S::setmodel_sync_poll, nullptr},
+      {"BBH_SETMODEL_TRACE", SET, 0, &S::setmodel_trace, nullptr},
+      {"BBH_SETMODEL_TRACE", IS, '2', &S::setmodel_trace_quiet, nullptr},
+      {"BBH_FIT_TRACE", SET, 0, &S::fit_trace, nullptr},
+      {"BBH_TILE_TRACE", SET, 0, &S::tile_trace, nullptr},
+      {"BBH_FLOW_TRACE", SET, 0, &S::flow_trace, nullptr},
+      {"BBH_TILE_STAMPS", SET, 0, &S::tile_stamps, nullptr},
+  };
+  bbh_switches sw;
+  for (const auto& row : table) {
+    const char* e = getenv(row.name);
+    if (!e) continue;
+    long long v = 1;  // SET
+    if (row.parse == NOT) v = e[0] != row.c;
+    if (row.parse == IS) v = e[0] == row.c;
+    if (row.parse == INT) v = atoi(e);
+    if (row.parse == MB) v = std::min<long long>(std::max(1LL, atoll(e)), INT_MAX);
+    if (row.flag) sw.*row.flag = v != 0;
+    if (row.num) sw.*row.num = (int)v;
+  }
+  return sw;
+}
+
+hipError_t bbh_allow_lds(int device, const void* kernel, size_t bytes) {
+  if (bytes <= BBH_LDS_DEFAULT_LIMIT) return hipSuccess;
+  hipError_t e = device < 0 ? hipGetDevice(&device) : hipSuccess;
+  if (e != hipSuccess) return e;
+  static std::mutex mu;
+  static std::map<std::pair<const void*, int>, size_t> granted;  // (kernel, device) -> bytes
+  std::lock_guard<std::mutex> lock(mu);
+  size_t& have = granted[{kernel, device}];
+  if (bytes <= have) return hipSuccess;
+  e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  if (e == hipSuccess) have = bytes;
+  return e;
+}
 
 extern "C" int bbh_create(int device_id, bbh_handle** out) {
   if (!out) return -1;
@@ -27,32 +119,7 @@ extern "C" int bbh_create(int device_id, bbh_handle** out) {
     int v = 0;
     if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, device_id) == hipSuccess && v > 0) h->lds_per_block = (size_t)v;
   }
-  if (const char* e = getenv("BBH_PENDING_LDS")) h->pending_lds_form = (e[0] != '0');
-  if (const char* e = getenv("BBH_FIT_GRAPH")) h->fit_graph_mode = (e[0] != '0');
-  if (const char* e = getenv("BBH_FIT_SMALL")) h->fit_small = (e[0] != '0');
-  if (const char* e = getenv("BBH_FIT_FLOW")) h->fit_flow = atoi(e);
-  if (const char* e = getenv("BBH_FLOW_SPIN")) h->flow_spin_limit = atoi(e);
-  if (const char* e = getenv("BBH_TILE_GRAM")) h->tile_gram = (e[0] != '0');
-  if (const char* e = getenv("BBH_TILE_WT")) h->tile_wt = (e[0] != '0');
-  if (const char* e = getenv("BBH_TILE_ACQ")) h->tile_d_sc1 = (e[0] == '0');  // (default: acquire fence)
-  if (const char* e = getenv("BBH_TILE_MT")) {
-    h->tile_mt = (e[0] != '0');
-    h->tile_mt_partial = (e[0] == 'p');
-  }
-  if (const char* e = getenv("BBH_POTRF_TILES")) h->potrf_tiles = (e[0] != '0');
-  if (const char* e = getenv("BBH_TILE_SPIN")) h->tile_spin_limit = atoi(e);
-  if (const char* e = getenv("BBH_KV_GLOBAL")) h->kv_global_mode = (e[0] != '0') ? 1 : 0;
-  if (const char* e = getenv("BBH_KV_LDS")) h->kv_lds_blocks = atoi(e);
-  if (const char* e = getenv("BBH_MEAN_VALU")) h->use_mean_valu = (e[0] != '0');
-  if (const char* e = getenv("BBH_COOPG_CROSS")) h->coopg_cross_on = (e[0] != '0');
-  if (const char* e = getenv("BBH_KVCACHE")) h->use_kvcache = (e[0] != '0');
-  if (const char* e = getenv("BBH_PIPELINE")) h->use_pipeline = (e[0] != '0');  // A/B switch, default on
-  if (const char* e = getenv("BBH_COOP")) h->coop_mode = atoi(e);
-  if (const char* e = getenv("BBH_POTRF_REG")) h->potrf_register_form = (e[0] != '0');
-  if (const char* e = getenv("BBH_FIT_OVERLAP")) h->fit_overlap = (e[0] != '0');
-  if (const char* e = getenv("BBH_Q1_SLICED")) h->q1_sliced = (e[0] != '0');
-  if (const char* e = getenv("BBH_SELECT")) h->select_on = (e[0] != '0');
-  if (const char* e = getenv("BBH_SMALL")) h->small_on = (e[0] != '0');
+  h->sw = bbh_read_switches();
   *out = h;
   return 0;
 }

@@ -3,6 +3,7 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <limits.h>
 #include <stdint.h>
 
 #include <string>
@@ -190,8 +191,65 @@ __device__ __forceinline__ double bbh_kcomp(const bbh_kern_spec& ks, const doubl
   return bbh_combine(ks.F, ks.combine, ks.grp, u);
 }
 
+// Run-time switches of the native library: one member per BBH_* environment variable, its default as the initialiser.
+// bbh_read_switches (bbh_api.hip) fills the struct when a handle is created; nothing writes it afterwards.
+struct bbh_switches {
+  // ---- fused posterior ----
+  bool use_pipeline = true;       // BBH_PIPELINE=0: plain form instead of the software-pipelined fused kernel (A/B)
+  bool use_mean_valu = true;      // BBH_MEAN_VALU=0: mean contraction through the MFMA form (A/B)
+  bool use_kvcache = true;        // BBH_KVCACHE=0: recompute kernel values in every pass (A/B)
+  int kv_global_mode = -1;        // BBH_KV_GLOBAL: 0 never use global slabs, 1 always, unset: by size
+  int kv_lds_blocks = -1;         // BBH_KV_LDS: cap on LDS-cached k-blocks per wave (-1 = as many as fit)
+  int coop_mode = 1;              // BBH_COOP: 0 never use the cooperative form, 1 where it pays (default), 2 wherever instantiated
+  bool coop_small = true;         // BBH_COOP_SMALL=0: the eight-round cooperative instantiation for small models too (A/B)
+  bool coopg_cross_on = true;     // BBH_COOPG_CROSS=0: composite models' mean-only / cross passes through the materialised path (A/B)
+  bool small_on = true;           // BBH_SMALL=0: keep the cooperative form for n <= 64 (A/B)
+  bool small_force = false;       // BBH_SMALL_FORCE=1: the register-resident form whatever the candidate count
+  bool columns_coop = true;       // BBH_COLUMNS_COOP=0: the plain kernel for every column group (A/B)
+  int columns_nt = 2;             // BBH_COLUMNS_NT=1: one candidate tile per workgroup of the cooperative columns kernel (A/B)
+  // ---- acquisition and selection ----
+  bool pending_lds_form = false;  // BBH_PENDING_LDS=1: generic LDS form of the pending qLogEI kernel (A/B)
+  int pending_slices = INT_MIN;   // BBH_PENDING_SLICES: sample slices of the pending qLogEI kernel (unset: by size)
+  int qbig_ws_mb = 0;             // BBH_QBIG_WS_MB: workspace bound of the chunked joint qLogEI in MB, at least 1 (unset: the built-in bound)
+  bool q1_sliced = true;          // BBH_Q1_SLICED=0: q' = 1 qLogEI as one thread per candidate (A/B)
+  bool nehvi_log = false;         // BBH_NEHVI_LOG=1: log-domain sums of qLogNEHVI instead of the linear-domain ones
+  int nehvi_slices = INT_MIN;     // BBH_NEHVI_SLICES: sample slices of the linear-domain qLogNEHVI kernel (unset: by size)
+  bool nehvi_pk = true;           // BBH_NEHVI_PK=0: double-precision fat-minimum factors in the linear-domain qLogNEHVI kernel (A/B)
+  bool select_on = true;          // BBH_SELECT=0: top-k / argmax by k rounds of workgroup argmax (A/B)
+  bool select_mapped = true;      // BBH_SELECT_MAPPED=0: selection results through a device buffer + copy instead of host-mapped stores (A/B)
+  // ---- fit evaluation ----
+  bool fit_graph_mode = false;    // BBH_FIT_GRAPH=1: replay the captured graph (slower, see bbh_model.hip)
+  bool fit_overlap = true;        // BBH_FIT_OVERLAP=0: the inverse of the factor strictly after the factorisation (A/B)
+  bool fit_small = true;          // BBH_FIT_SMALL=0: evaluations of small models (np = 64, one task, one kernel, MLL) launch by launch instead of the fused one-workgroup kernel
+  int fit_flow = 1;               // BBH_FIT_FLOW: 0 fit evaluations for 64 < np <= 1024 launch by launch, 1 (default) Gram + factorisation launches, then ONE dataflow launch for K^-1, alpha, value and gradient, 2 the whole evaluation as one dataflow launch
+  int flow_spin_limit = 1 << 17;  // BBH_FLOW_SPIN: polls before a waiting role of the dataflow fit evaluation gives up
+  bool fit_post1 = true;          // BBH_FIT_POST1=0: the two-per-CU form of the launch behind the factorisation (A/B)
+  bool fit_tail1 = true;          // BBH_FIT_TAIL1=0: the two-per-CU form of the dataflow tail (A/B)
+  bool potrf_tiles = true;        // BBH_POTRF_TILES=0: per-step launches instead of the one-launch tile-dataflow factorisation (np <= 1024)
+  bool potrf_register_form = false;  // BBH_POTRF_REG=1: 64x64 diagonal blocks by the one-wave register kernel (A/B)
+  int tile_spin_limit = 1 << 17;  // BBH_TILE_SPIN: polls (~1 us each) before a waiting tile gives up (a whole factorisation takes ~200 us)
+  bool tile_d_sc1 = false;        // BBH_TILE_ACQ=0: row heads take D_{I-1} through sc1 loads without an acquire fence (valid after write-through stores; measured: no gain, so the fence form stays the default)
+  bool tile_wt = true;            // BBH_TILE_WT=0: tiles handed between workgroups through plain stores + an agent-scope release fence instead of write-through (sc1) stores (A/B)
+  bool tile_mt = true;            // BBH_TILE_MT=0: K^-1's tiles stay in the dataflow tail (A/B)
+  bool tile_mt_partial = false;   // BBH_TILE_MT=partial
+  bool tile_gram = true;          // BBH_TILE_GRAM=0: fit evaluations launch bbh_gram_kernel before the factorisation instead of building the tiles inside it (A/B)
+  bool tile_gram_theta_copy = false;  // BBH_TILE_GRAM_THETA=copy: theta by one H2D copy and device reads instead of kernel arguments (A/B)
+  // ---- set_model ----
+  bool setmodel_upload_copy = false;  // BBH_SETMODEL_UPLOAD=copy: four copy-engine copies from the staging buffer instead of the scatter kernel
+  bool setmodel_sync = true;      // BBH_SETMODEL_SYNC=0: bbh_set_model returns without waiting for the upload
+  bool setmodel_sync_poll = false;    // BBH_SETMODEL_SYNC=poll: wait by polling instead of a stream synchronisation
+  // ---- traces on stderr / debug stamps ----
+  bool setmodel_trace = false;        // BBH_SETMODEL_TRACE: wall-clock stamps of bbh_set_model's stages
+  bool setmodel_trace_quiet = false;  // BBH_SETMODEL_TRACE=2: the stamps printed in one piece when the call returns
+  bool fit_trace = false;         // BBH_FIT_TRACE: host time of a fit evaluation spent enqueueing vs waiting
+  bool tile_trace = false;        // BBH_TILE_TRACE: a line whenever a dataflow launch gives up
+  bool flow_trace = false;        // BBH_FLOW_TRACE: clock stamps of the dataflow fit evaluation's roles
+  bool tile_stamps = false;       // BBH_TILE_STAMPS: clock stamps of the Gram-building tile launch
+};
+
 struct bbh_handle {
   int device = 0;
+  bbh_switches sw;  // read once, in bbh_create
   hipStream_t stream = nullptr;
   std::string err;
 
@@ -253,7 +311,6 @@ struct bbh_handle {
   double* d_tasktbl = nullptr;    // [T, T] outputscale * B (or [1] = outputscale)
   int* d_taskext = nullptr;       // [np_ext] task id per (training | pending) point
   int64_t rfrag_elems = 0;
-  bool use_pipeline = true;       // software-pipelined fused kernel (env BBH_PIPELINE=0 -> plain form, for A/B)
   int64_t* d_pass_off = nullptr;  // [npass] element offsets of the passes in d_rfrag
   int* d_pass_w = nullptr;        // [npass] pass widths (16-column blocks)
   int npass = 0;
@@ -261,32 +318,22 @@ struct bbh_handle {
   double* d_kvcache = nullptr;    // kernel-value cache of the multi-pass fused kernel (grow-only)
   size_t kvcache_bytes = 0;
   int* d_slab_flags = nullptr;    // claim flags of the cache slabs (zero = free)
-  bool coopg_cross_on = true;     // env BBH_COOPG_CROSS=0: composite models' mean-only / cross passes through the materialised path (A/B)
-  bool use_mean_valu = true;      // env BBH_MEAN_VALU=0: mean contraction through the MFMA form (A/B)
-  bool use_kvcache = true;        // env BBH_KVCACHE=0: recompute kernel values in every pass (A/B)
   size_t lds_per_block = 65536;   // LDS a workgroup may use (device property; 160 KB on gfx950)
-  bool pending_lds_form = false;  // env BBH_PENDING_LDS=1: generic LDS form of the pending qLogEI kernel (A/B)
-  int kv_global_mode = -1;        // env BBH_KV_GLOBAL: 0 never use global slabs, 1 always, unset: by size
-  int kv_lds_blocks = -1;         // env BBH_KV_LDS: cap on LDS-cached k-blocks per wave (-1 = as many as fit)
   int num_cu = 256;               // compute units of the device (sizes the slab pool of the kernel-value cache)
   int wmax = 16;                  // column blocks per pass of the windowed fused kernel (two waves per SIMD)
-  bool fit_overlap = true;        // env BBH_FIT_OVERLAP=0: the inverse of the factor strictly after the factorisation (A/B)
   hipStream_t side_stream = nullptr;  // second stream of the fit (rows of L^-1 next to the trailing updates)
   hipStream_t fit_stream = nullptr;   // stream the captured evaluation graph is replayed on
-  int fit_small = 1;  // env BBH_FIT_SMALL=0: evaluations of small models (np = 64, one task, one kernel, MLL) launch by launch instead of the fused one-workgroup kernel
-  bool fit_small_ready = false;
-  bool potrf_tiles = true, tiles_ready = false;  // env BBH_POTRF_TILES=0: per-step launches instead of the one-launch tile-dataflow factorisation (np <= 1024)
-  int tile_spin_limit = 1 << 17, tile_spin_limit_set = -1;  // env BBH_TILE_SPIN: polls (~1 us each) before a waiting tile gives up (a whole factorisation takes ~200 us)
+  bool fit_small_ready = false, fit_small_failed = false;  // failed: the fused small-model evaluation could not be set up, launch by launch from now on
+  bool tiles_ready = false, tiles_gave_up = false;  // gave up: a tile-dataflow launch could not be set up or ran out of polls, per-step path from now on
+  int tile_spin_limit_set = -1;  // the poll budget the device symbol holds
   int tiles_per_device = 0;           // workgroups of the tile kernel the device holds at once (occupancy x CUs)
   int* d_tileflags = nullptr;         // [2][16][16] publish flags of the L- and X-tiles (epoch-stamped)
   int tile_epoch = 0;
   hipGraphExec_t fit_exec = nullptr;  // one evaluation of the fit objective, captured per model (bbh_fit_value_grad)
-  bool fit_graph_mode = false, fit_graph_failed = false;  // env BBH_FIT_GRAPH=1: replay the captured graph (slower, see bbh_model.hip)
+  bool fit_graph_failed = false;
   double *pin_theta = nullptr, *pin_out = nullptr;  // pinned staging of the evaluation (theta in, value + gradient out)
   int* pin_info = nullptr;
   hipEvent_t side_events[2] = {nullptr, nullptr};
-  bool potrf_register_form = false;  // env BBH_POTRF_REG=1: 64x64 diagonal blocks by the one-wave register kernel (A/B)
-  int coop_mode = 1;              // env BBH_COOP: 0 never use the cooperative form, 1 where it pays (default), 2 wherever instantiated
   bool coop_ready = false;        // operand slices of the cooperative form are packed for the current factorisation
   bool coopg_ready = false;       // ... of the cooperative form with the generic production (composite / RQ / piecewise models, bbh_coopg.h)
   double* d_trainfrag_f = nullptr;  // [F][nb + 1][kd][64] per-factor training fragments (coopg)
@@ -329,32 +376,23 @@ struct bbh_handle {
   void* comm_state = nullptr;     // RCCL communicator + exchange buffers (bbh_comm.hip), null until bbh_comm_init
   double* d_rsmall = nullptr;     // register-resident small-model form (bbh_small.h): fragments of the lower triangle of L^-T
   int small_nb = 0;               // its training blocks ceil(n / 16) <= 4 once the operands are packed (0: form not available)
-  bool small_on = true;           // env BBH_SMALL=0: keep the cooperative form for n <= 64 (A/B)
   int64_t slice_rows = 0;         // bbh_set_slice_rows: row count the sample-slice heuristics use instead of the local N (0: local)
   void* flow_state = nullptr;     // roles, flags and scratch of the one-launch fit evaluation (bbh_fitflow.hip)
-  int flow_spin_limit = 1 << 17;  // env BBH_FLOW_SPIN: polls before a waiting role of the dataflow fit evaluation gives up
+  bool flow_gave_up = false;      // a dataflow fit evaluation could not be set up or never reported: launch by launch from now on
   bool skip_x_memset = false;     // bbh_potrf_trtri: leave the upper tiles of L^-1 alone (the caller reads lower tiles only)
   bool flow_in_flight = false;    // the evaluation on the stream is the one-launch form (its flag needs the sentinel check)
-  long long* d_tiledbg = nullptr; // BBH_TILE_STAMPS=1: clock stamps of the Gram-building tile launch
+  long long* d_tiledbg = nullptr; // sw.tile_stamps: clock stamps of the Gram-building tile launch
   int tiledbg_n = 0;
-  bool tile_d_sc1 = false;        // env BBH_TILE_ACQ=0: row heads take D_{I-1} through sc1 loads without an acquire fence (valid after write-through stores; measured: no gain, so the fence form stays the default)
-  bool tile_wt = true;            // env BBH_TILE_WT=0: tiles handed between workgroups through plain stores + an agent-scope release fence instead of write-through (sc1) stores (A/B)
   int tiles_did_mt = 0;           // tiles of K^-1 the last tile-dataflow launch built itself (bbh_potrf_trtri_from_inputs with mt_args; block row 0 first)
   int tiles_mt_asked = 0;         // ... and how many it was asked for (bbh_last_fit_form: all of them or a part)
   bool potrf_tiles_ran = false;   // the last bbh_potrf_trtri was the tile-dataflow launch (false: per-step launches)
-  bool tile_mt_partial = false;   // env BBH_TILE_MT=partial
-  bool tile_mt = true;            // env BBH_TILE_MT=0: K^-1's tiles stay in the dataflow tail (A/B)
   bool info_clean = false;        // the Cholesky flag on the device is known to be 0 (the dataflow tail's last role resets it)
-  bool tile_gram = true;          // env BBH_TILE_GRAM=0: fit evaluations launch bbh_gram_kernel before the factorisation instead of building the tiles inside it (A/B)
-  int fit_flow = 1;               // env BBH_FIT_FLOW: 0 fit evaluations for 64 < np <= 1024 launch by launch, 1 (default) Gram + factorisation launches, then ONE dataflow launch for K^-1, alpha, value and gradient, 2 the whole evaluation as one dataflow launch
   void* rff_state = nullptr;      // feature-space model of the RFF kernel (bbh_rff.hip), null for every other kernel
   std::vector<double> rff_w_host; // bbh_set_rff_weights: the frequencies [dn, D] the next bbh_set_model with BBH_KERNEL_RFF takes
   int rff_w_dn = 0, rff_w_D = 0;
   void* nehvi_state = nullptr;    // device-resident box decompositions + their scratch (bbh_nehvi.hip), null until bbh_cells_build_dev
   void* select_state = nullptr;   // chunk keys, result block and base-sample tables of the selection kernels (bbh_select.hip)
   void* sobol_state = nullptr;    // staging of the device-side base-sample draw (bbh_sobol.hip), null until bbh_sobol_normal_dev
-  bool q1_sliced = true;          // env BBH_Q1_SLICED=0: q' = 1 qLogEI as one thread per candidate (A/B)
-  bool select_on = true;          // env BBH_SELECT=0: top-k / argmax by k rounds of workgroup argmax (A/B)
   // timing
   int timing = 0;  // 0 off, 1 every kernel family, otherwise 2 x (bit mask of the families that record events)
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -388,6 +426,12 @@ struct bbh_timed_scope {
 };
 
 inline int64_t bbh_round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
+
+// Dynamic LDS beyond the default limit has to be requested per kernel and per DEVICE.  Raises `kernel`'s limit on `device` (-1: the
+// current one, which is also the one the call acts on) to at least `bytes` unless it was granted that already; a no-op up to the
+// default.  Returns the HIP status of the request; callable from several host threads (bbh_api.hip).
+#define BBH_LDS_DEFAULT_LIMIT ((size_t)48 * 1024)
+__attribute__((visibility("hidden"))) hipError_t bbh_allow_lds(int device, const void* kernel, size_t bytes);
 
 // Device-resident box decompositions of one qLogNEHVI selection step (bbh_nehvi.hip: bbh_cells_build_dev writes them,
 // bbh_qlognehvi_cells in bbh_acq.hip scores against them).

@@ -440,7 +440,7 @@ __global__ __launch_bounds__(256, (GMIN >= 6 ? 5 : GMIN >= 4 ? 4 : BBH_COOP_WAVE
 // Instantiations (bbh_fused_coop_a.hip: 2, 4, 6 k-steps of the distance GEMM; _b: 8, 12, 16): Matérn-5/2 with and
 // without the task / outputscale table, RBF with and without, Matérn-3/2 without.
 // false: no instantiation for this model; grid.x == 0 only asks.
-bool bbh_coop_launch(int kd, int kind, bool has_tbl, dim3 grid, size_t lds, hipStream_t s, const CoopArgs& a);
+bool bbh_coop_launch(int kd, int kind, bool has_tbl, dim3 grid, size_t lds, hipStream_t s, const CoopArgs& a, bool small_ok);
 bool bbh_coop_launch_a(int kd, int kind, bool has_tbl, dim3 grid, size_t lds, hipStream_t s, const CoopArgs& a);
 bool bbh_coop_launch_b(int kd, int kind, bool has_tbl, dim3 grid, size_t lds, hipStream_t s, const CoopArgs& a);
 // n <= 256 (g0 >= 4): the four-round instantiations (Matérn-5/2 with and without table; 2, 4, 6, 8 k-steps)

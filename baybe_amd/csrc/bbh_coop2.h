@@ -283,10 +283,10 @@ bool bbh_coop2_launch_b(int kd, int kind, bool has_tbl, dim3 grid, size_t lds, h
     if (kind != BBH_KERNEL_MATERN52) return false;                                                             \
     if (grid.x == 0) return true;                                                                              \
     if (has_tbl) {                                                                                             \
-      BBH_FUSED_ALLOW_LDS((bbh_coop2_posterior_kernel<KDV, 1>), lds);                                          \
+      (void)bbh_allow_lds(-1, (const void*)bbh_coop2_posterior_kernel<KDV, 1>, lds);                           \
       hipLaunchKernelGGL((bbh_coop2_posterior_kernel<KDV, 1>), grid, dim3(256), lds, s, a);                    \
     } else {                                                                                                   \
-      BBH_FUSED_ALLOW_LDS((bbh_coop2_posterior_kernel<KDV, 0>), lds);                                          \
+      (void)bbh_allow_lds(-1, (const void*)bbh_coop2_posterior_kernel<KDV, 0>, lds);                           \
       hipLaunchKernelGGL((bbh_coop2_posterior_kernel<KDV, 0>), grid, dim3(256), lds, s, a);                    \
     }                                                                                                          \
     return true;                                                                                               \

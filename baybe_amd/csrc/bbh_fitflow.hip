@@ -834,15 +834,15 @@ void bbh_flow_destroy(bbh_handle* h) {
 void bbh_flow_mark_failed(bbh_handle* h) {
   bbh_flow_state* st = (bbh_flow_state*)h->flow_state;
   if (st) st->failed = true;
-  h->fit_flow = false;
+  h->flow_gave_up = true;
 }
 
 // models the dataflow forms take (the launch itself can still fail on resources: then the handle stops using them)
 bool bbh_fit_flow_eligible(bbh_handle* h) {
   const int64_t np = h->np;
   const bbh_flow_state* st = (const bbh_flow_state*)h->flow_state;
-  return h->fit_flow && np > 64 && np <= 64 * FF_MAXBLK && h->F <= 1 && !h->hadamard && h->dn <= FF_MAXD && h->T <= FF_MAXT && bbh_theta_len(h) <= 49 &&
-         h->desc.kernel_kind != BBH_KERNEL_PERIODIC && !h->fit_graph_mode && !(h->fit_stream && h->stream == h->fit_stream) && !(st && st->failed);
+  return h->sw.fit_flow && !h->flow_gave_up && np > 64 && np <= 64 * FF_MAXBLK && h->F <= 1 && !h->hadamard && h->dn <= FF_MAXD && h->T <= FF_MAXT && bbh_theta_len(h) <= 49 &&
+         h->desc.kernel_kind != BBH_KERNEL_PERIODIC && !h->sw.fit_graph_mode && !(h->fit_stream && h->stream == h->fit_stream) && !(st && st->failed);
 }
 
 // true: the evaluation is on the stream (theta_dev / out_dev / info_dev are the device views of the pinned staging buffers)
@@ -903,9 +903,9 @@ bool bbh_fit_flow_launch(bbh_handle* h, const double* theta_dev, double* out_dev
     int per_cu = 0, per_cu_b = 0;
     const void* kfn = tail_only ? (const void*)bbh_fit_tail_kernel : (split ? (const void*)bbh_fit_factor_kernel : (const void*)bbh_fit_flow_kernel);
     const size_t lds_b = sizeof(double) * 2 * 64 * PD_LD;
-    bool ok = hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess &&
+    bool ok = bbh_allow_lds(h->device, kfn, lds) == hipSuccess &&
               hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfn, 256, lds) == hipSuccess && per_cu >= 1 &&
-              (!split || (hipFuncSetAttribute((const void*)bbh_fit_post_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b) == hipSuccess &&
+              (!split || (bbh_allow_lds(h->device, (const void*)bbh_fit_post_kernel, lds_b) == hipSuccess &&
                           hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_b, (const void*)bbh_fit_post_kernel, 256, lds_b) == hipSuccess && per_cu_b >= 1)) &&
               hipMalloc((void**)&st->d_roles, sizeof(int) * roles.size()) == hipSuccess &&
               hipMemcpy(st->d_roles, roles.data(), sizeof(int) * roles.size(), hipMemcpyHostToDevice) == hipSuccess &&
@@ -989,13 +989,13 @@ bool bbh_fit_flow_launch(bbh_handle* h, const double* theta_dev, double* out_dev
   fa.nM = st->nM;
   fa.nG = st->nG;
   fa.epoch = ++st->epoch;
-  fa.spin = h->flow_spin_limit;
+  fa.spin = h->sw.flow_spin_limit;
   fa.tail_only = tail_only ? 1 : 0;
   fa.info = h->d_info;
   fa.abort = tail_only ? st->d_flags + FF_COUNTERS + 3 : h->d_info;
   fa.out = out_dev;
   fa.info_out = info_dev;
-  if (getenv("BBH_FLOW_TRACE")) {
+  if (h->sw.flow_trace) {
     if (!st->d_dbg && hipMalloc((void**)&st->d_dbg, sizeof(long long) * 8 * 1024) != hipSuccess) st->d_dbg = nullptr;
     fa.dbg = st->d_dbg;
   }
@@ -1041,11 +1041,10 @@ bool bbh_fit_flow_launch(bbh_handle* h, const double* theta_dev, double* out_dev
   if (skip_mt >= st->nM) {  // the table starts with the nM M-tile roles: begin behind them (their count was added by the factorisation's workgroups)
     int per_cu_b = 0;
     const int nB = st->nroles - st->nA;
-    static const bool post1_ok = !(getenv("BBH_FIT_POST1") && getenv("BBH_FIT_POST1")[0] == '0');  // (A/B)
-    const bool one_per_cu = post1_ok && nB <= h->num_cu;
+    const bool one_per_cu = h->sw.fit_post1 && nB <= h->num_cu;
     const void* pk = one_per_cu ? (const void*)bbh_fit_post1_kernel : (const void*)bbh_fit_post_kernel;
     if (!st->gridB) {
-      if (hipFuncSetAttribute(pk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
+      if (bbh_allow_lds(h->device, pk, lds) != hipSuccess ||
           hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_b, pk, 256, lds) != hipSuccess || per_cu_b < 1) {
         (void)hipGetLastError();
         return false;
@@ -1072,13 +1071,12 @@ bool bbh_fit_flow_launch(bbh_handle* h, const double* theta_dev, double* out_dev
   // one workgroup per CU without the 256-register cap (the two-per-CU form spills 99 VGPRs: 400 B of scratch per lane); measured at
   // n = 1024: 464 -> 450 us per evaluation, ICM / LOO 552 -> 537 us although its 848 roles then share 256 slots instead of 512
   // (profiles/r06_fit_eval_post1_tail1.log).  BBH_FIT_TAIL1=0: the two-per-CU form (A/B)
-  static const bool tail1 = !(getenv("BBH_FIT_TAIL1") && getenv("BBH_FIT_TAIL1")[0] == '0');
-  if (tail_only && tail1) {
-    static bool attr1 = false;
-    if (!attr1) {
-      hipFuncSetAttribute((const void*)bbh_fit_tail1_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      attr1 = true;
-    }
+  bool tail1 = tail_only && h->sw.fit_tail1;
+  if (tail1 && bbh_allow_lds(h->device, (const void*)bbh_fit_tail1_kernel, lds) != hipSuccess) {
+    (void)hipGetLastError();  // (no LDS for it on this device: the two-per-CU form, whose limit the state's set-up raised)
+    tail1 = false;
+  }
+  if (tail1) {
     const int g1 = st->nroles < h->num_cu ? st->nroles : h->num_cu;
     hipLaunchKernelGGL(bbh_fit_tail1_kernel, dim3((unsigned)g1), dim3(256), lds, h->stream, fa);
     if (hipGetLastError() != hipSuccess) {
@@ -1115,7 +1113,7 @@ void bbh_fit_flow_reset(bbh_handle* h) {
   hipMemset(h->d_info, 0, sizeof(int));
   st->ticket_base = st->doneM_base = st->doneG_base = st->doneV_base = 0;
   st->failed = true;
-  h->fit_flow = false;
+  h->flow_gave_up = true;
 }
 
 // The M-tile arguments of the NEXT tail launch of this model (state created if need be): what the factorisation launch needs to build

@@ -3,7 +3,7 @@
 
 #define BBH_LAUNCH(TBL, KND)                                                                      \
   do {                                                                                            \
-    BBH_FUSED_ALLOW_LDS((bbh_fused_posterior_kernel<TBL, KND, 16>), lds);                          \
+    (void)bbh_allow_lds(-1, (const void*)bbh_fused_posterior_kernel<TBL, KND, 16>, lds);           \
     hipLaunchKernelGGL((bbh_fused_posterior_kernel<TBL, KND, 16>), grid, block, lds, s, a);        \
   } while (0)
 

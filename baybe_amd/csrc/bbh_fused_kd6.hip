@@ -3,7 +3,7 @@
 
 #define BBH_LAUNCH(TBL, KND)                                                                      \
   do {                                                                                            \
-    BBH_FUSED_ALLOW_LDS((bbh_fused_posterior_kernel<TBL, KND, 6>), lds);                          \
+    (void)bbh_allow_lds(-1, (const void*)bbh_fused_posterior_kernel<TBL, KND, 6>, lds);           \
     hipLaunchKernelGGL((bbh_fused_posterior_kernel<TBL, KND, 6>), grid, block, lds, s, a);        \
   } while (0)
 

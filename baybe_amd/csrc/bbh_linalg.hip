@@ -422,7 +422,7 @@ __global__ __launch_bounds__(256) void bbh_potrf_tiles_kernel(double* A, int64_t
 }
 
 void bbh_ensure_side_stream(bbh_handle* h) {
-  if (!h->fit_overlap || h->side_stream) return;
+  if (!h->sw.fit_overlap || h->side_stream) return;
   if (hipStreamCreateWithFlags(&h->side_stream, hipStreamNonBlocking) != hipSuccess) h->side_stream = nullptr;
   for (auto& e : h->side_events)
     if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) e = nullptr;
@@ -518,25 +518,25 @@ static bool bbh_potrf_tiles(bbh_handle* h, const double* gram_theta = nullptr, c
   h->info_clean = false;  // (whatever runs next may leave a failure flag behind; only a finished dataflow tail re-establishes it)
   const int64_t np = h->np;
   const int nbk = (int)(np / 64);
-  if (!h->potrf_tiles || nbk > 16 || g_tiles_unusable[h->device & 63]) return false;
+  if (!h->sw.potrf_tiles || h->tiles_gave_up || nbk > 16 || g_tiles_unusable[h->device & 63]) return false;
   // Never inside a stream capture (BBH_FIT_GRAPH=1): the epoch is a by-value kernel argument, so every replay of the captured
   // launch would wait for the flag value the previous replay already left behind (all waits pass at once, tiles read
   // unfinished blocks), and the one-time set-up below must not run while capturing.  The captured evaluation uses the
   // per-step launches.
-  if (h->fit_graph_mode || (h->fit_stream && h->stream == h->fit_stream)) return false;
+  if (h->sw.fit_graph_mode || (h->fit_stream && h->stream == h->fit_stream)) return false;
   const int ntiles = nbk + (nbk - 1) * (nbk - 2) / 2 + nbk * (nbk - 1) / 2;  // row heads, other L-tiles, X-tiles
   static const size_t lds = sizeof(double) * 4 * 64 * PD_LD;  // 135 KB: one workgroup per CU
   if (!h->tiles_ready) {
     int per_cu = 0;
-    if (hipFuncSetAttribute((const void*)bbh_potrf_tiles_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
-        hipFuncSetAttribute((const void*)bbh_potrf_tiles_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
-        hipFuncSetAttribute((const void*)bbh_potrf_tiles_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
-        hipFuncSetAttribute((const void*)bbh_potrf_tiles_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
+    if (bbh_allow_lds(h->device, (const void*)bbh_potrf_tiles_kernel<false, false>, lds) != hipSuccess ||
+        bbh_allow_lds(h->device, (const void*)bbh_potrf_tiles_kernel<true, false>, lds) != hipSuccess ||
+        bbh_allow_lds(h->device, (const void*)bbh_potrf_tiles_kernel<false, true>, lds) != hipSuccess ||
+        bbh_allow_lds(h->device, (const void*)bbh_potrf_tiles_kernel<true, true>, lds) != hipSuccess ||
         hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)bbh_potrf_tiles_kernel<true, true>, 256, lds) != hipSuccess ||
         hipMalloc((void**)&h->d_tileflags, sizeof(int) * 2 * 16 * 16 * PD_FLAG_STRIDE) != hipSuccess ||
         hipMemset(h->d_tileflags, 0, sizeof(int) * 2 * 16 * 16 * PD_FLAG_STRIDE) != hipSuccess) {
       (void)hipGetLastError();
-      h->potrf_tiles = false;
+      h->tiles_gave_up = true;
       return false;
     }
     h->tiles_per_device = per_cu * h->num_cu;  // workgroups of this kernel the device can hold at once
@@ -548,18 +548,18 @@ static bool bbh_potrf_tiles(bbh_handle* h, const double* gram_theta = nullptr, c
     ma = *mt;
     // (a part of them - block row 0 first - is possible and handled by the tail (skip_mt), but measured without gain at n = 1024, where the
     // tail's gradient roles, not K^-1, are the long pole: BBH_TILE_MT=partial)
-    if (ntiles + ma.nM > h->tiles_per_device) ma.nM = h->tile_mt_partial ? h->tiles_per_device - ntiles : 0;
+    if (ntiles + ma.nM > h->tiles_per_device) ma.nM = h->sw.tile_mt_partial ? h->tiles_per_device - ntiles : 0;
   }
   h->tiles_did_mt = ma.nM;
   h->tiles_mt_asked = mt ? mt->nM : 0;
   const int grid_tiles = ntiles + ma.nM;
-  if (h->tile_spin_limit != h->tile_spin_limit_set) {
-    if (hipMemcpyToSymbol(HIP_SYMBOL(pd_spin_limit), &h->tile_spin_limit, sizeof(int)) != hipSuccess) {
+  if (h->sw.tile_spin_limit != h->tile_spin_limit_set) {
+    if (hipMemcpyToSymbol(HIP_SYMBOL(pd_spin_limit), &h->sw.tile_spin_limit, sizeof(int)) != hipSuccess) {
       (void)hipGetLastError();
-      h->potrf_tiles = false;
+      h->tiles_gave_up = true;
       return false;
     }
-    h->tile_spin_limit_set = h->tile_spin_limit;
+    h->tile_spin_limit_set = h->sw.tile_spin_limit;
   }
   hipStream_t s = h->stream;
   if (!pd_ledger_reserve(h->device, s, grid_tiles, h->tiles_per_device)) {  // other streams' launches hold the device: per-step path this time
@@ -571,7 +571,7 @@ static bool bbh_potrf_tiles(bbh_handle* h, const double* gram_theta = nullptr, c
   if (!info_clean) hipMemsetAsync(h->d_info, 0, sizeof(int), s);
   const int epoch = ++h->tile_epoch;
   pd_gram_src gs{};
-  gs.d_sc1 = (h->tile_wt && h->tile_d_sc1) ? 1 : 0;
+  gs.d_sc1 = (h->sw.tile_wt && h->sw.tile_d_sc1) ? 1 : 0;
   if (gram_theta || gram_theta_host) {
     const bbh_kern_spec ks = bbh_kern_spec_of(h);
     gs.xnT = h->d_xnT;
@@ -589,16 +589,16 @@ static bool bbh_potrf_tiles(bbh_handle* h, const double* gram_theta = nullptr, c
     gs.use_os = ks.use_os;
     gs.jb = ks.jb;
     gs.alpha_off = ks.alpha_off;
-    if (getenv("BBH_TILE_STAMPS") && !h->d_tiledbg && hipMalloc((void**)&h->d_tiledbg, sizeof(long long) * 8 * 512) != hipSuccess) h->d_tiledbg = nullptr;
+    if (h->sw.tile_stamps && !h->d_tiledbg && hipMalloc((void**)&h->d_tiledbg, sizeof(long long) * 8 * 512) != hipSuccess) h->d_tiledbg = nullptr;
     gs.dbg = h->d_tiledbg;
     h->tiledbg_n = ntiles;
-    if (h->tile_wt)
+    if (h->sw.tile_wt)
       hipLaunchKernelGGL((bbh_potrf_tiles_kernel<true, true>), dim3((unsigned)grid_tiles), dim3(256), lds, s, h->d_K, np, nbk, h->d_D, h->d_X, np, h->d_tileflags,
                          h->d_tileflags + 256 * PD_FLAG_STRIDE, epoch, h->d_info, gs, ma);
     else
       hipLaunchKernelGGL((bbh_potrf_tiles_kernel<true, false>), dim3((unsigned)grid_tiles), dim3(256), lds, s, h->d_K, np, nbk, h->d_D, h->d_X, np, h->d_tileflags,
                          h->d_tileflags + 256 * PD_FLAG_STRIDE, epoch, h->d_info, gs, ma);
-  } else if (h->tile_wt) {
+  } else if (h->sw.tile_wt) {
     hipLaunchKernelGGL((bbh_potrf_tiles_kernel<false, true>), dim3((unsigned)grid_tiles), dim3(256), lds, s, h->d_K, np, nbk, h->d_D, h->d_X, np, h->d_tileflags,
                        h->d_tileflags + 256 * PD_FLAG_STRIDE, epoch, h->d_info, gs, ma);
   } else {
@@ -797,15 +797,15 @@ __global__ __launch_bounds__(256) void bbh_fit_small_kernel(const double* __rest
 }
 
 bool bbh_fit_small_launch(bbh_handle* h, double jitter, const double* theta_dev, double* out_dev, int* info_dev) {
-  if (!h->fit_small || h->np != 64 || h->T != 1 || h->F > 1 || h->hadamard || h->desc.criterion != BBH_CRITERION_MLL ||
-      h->dn > FS_MAXD || h->desc.kernel_kind == BBH_KERNEL_PERIODIC || h->fit_graph_mode ||
+  if (!h->sw.fit_small || h->fit_small_failed || h->np != 64 || h->T != 1 || h->F > 1 || h->hadamard || h->desc.criterion != BBH_CRITERION_MLL ||
+      h->dn > FS_MAXD || h->desc.kernel_kind == BBH_KERNEL_PERIODIC || h->sw.fit_graph_mode ||
       (h->fit_stream && h->stream == h->fit_stream))
     return false;
   static const size_t lds = sizeof(double) * (3 * 64 * PD_LD + FS_MAXD * 64 + 192 + FS_MAXD + 64 + 4 * (FS_MAXD + 8) + 64);
   if (!h->fit_small_ready) {
-    if (hipFuncSetAttribute((const void*)bbh_fit_small_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+    if (bbh_allow_lds(h->device, (const void*)bbh_fit_small_kernel, lds) != hipSuccess) {
       (void)hipGetLastError();
-      h->fit_small = 0;
+      h->fit_small_failed = true;
       return false;
     }
     h->fit_small_ready = true;
@@ -849,11 +849,11 @@ void bbh_potrf_trtri(bbh_handle* h) {
   //   X[I][0:I] = -D[I] (L[I][0:I] X[0:I][0:I])
   // - none of which the trailing update of step I touches.  Sequentially (sub-diagonal by sub-diagonal, after the
   // factorisation) these 14 small GEMM launches were 25 % of a fit evaluation at n = 512.
-  const bool overlap = h->fit_overlap;
+  const bool overlap = h->sw.fit_overlap;
   bbh_ensure_side_stream(h);
   hipStream_t s2 = (overlap && h->side_stream && h->side_events[0] && h->side_events[1]) ? h->side_stream : s;
   for (int64_t J = 0; J < nbk; J++) {
-    if (h->potrf_register_form)  // env BBH_POTRF_REG=1: the one-wave register form (A/B)
+    if (h->sw.potrf_register_form)  // env BBH_POTRF_REG=1: the one-wave register form (A/B)
       hipLaunchKernelGGL(bbh_potrf_diag_kernel, dim3(1), dim3(256), 0, s, A, np, J, h->d_D, h->d_X, np, h->d_info);
     else
       hipLaunchKernelGGL(bbh_potrf_diag16_kernel, dim3(1), dim3(256), 0, s, A, np, J, h->d_D, h->d_X, np, h->d_info);

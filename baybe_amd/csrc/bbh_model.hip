@@ -463,8 +463,7 @@ extern "C" int bbh_set_model_ex(bbh_handle* h, const bbh_model_desc* desc, int64
   // BBH_SETMODEL_TRACE=1: wall-clock stamps of the stages below on stderr (scripts/gpu_set_model_probe.py)
   // (=2: the stamps are kept and printed in one piece when the call returns - a write per stage shifts the timing of what follows:
   // with per-stage prints the call measured 0.2 ms, without them 18 ms, profiles/r06_small_space_latency*.log)
-  static const char* sm_env = getenv("BBH_SETMODEL_TRACE");
-  static const bool sm_trace = sm_env != nullptr, sm_quiet = sm_env && sm_env[0] == '2';
+  const bool sm_trace = h->sw.setmodel_trace, sm_quiet = h->sw.setmodel_trace_quiet;
   const auto sm_t0 = std::chrono::steady_clock::now();
   struct sm_rec { const char* what; double us; };
   sm_rec sm_log[16];
@@ -654,10 +653,8 @@ extern "C" int bbh_set_model_ex(bbh_handle* h, const bbh_model_desc* desc, int64
     hipStream_t s = h->stream;
     // BBH_SETMODEL_UPLOAD=copy: four hipMemcpyAsync from the staging buffer (copy engine); default: ONE kernel reads the staging buffer
     // through its device mapping and scatters the four arrays (and clears d_pendT) - no copy-engine command on this path
-    static const char* up_env = getenv("BBH_SETMODEL_UPLOAD");
-    static const char* sync_env = getenv("BBH_SETMODEL_SYNC");
     void* stage_dev = nullptr;
-    const bool by_kernel = !(up_env && up_env[0] == 'c') && hipHostGetDevicePointer(&stage_dev, stage, 0) == hipSuccess;
+    const bool by_kernel = !h->sw.setmodel_upload_copy && hipHostGetDevicePointer(&stage_dev, stage, 0) == hipSuccess;
     if (by_kernel) {
       bbh_scatter_args sa{};
       sa.src = (const unsigned char*)stage_dev;
@@ -698,11 +695,11 @@ extern "C" int bbh_set_model_ex(bbh_handle* h, const bbh_model_desc* desc, int64
     // (complete before the call returns, as the synchronous copies were: the handle's stream may be changed before the model is used -
     // bbh_set_stream, the captured-graph stream of BBH_FIT_GRAPH - and the side streams are not ordered behind h->stream)
     sm_stamp("enqueued");
-    if (sync_env && sync_env[0] == 'p') {  // poll
+    if (h->sw.setmodel_sync_poll) {  // poll
       hipError_t q;
       while ((q = hipStreamQuery(s)) == hipErrorNotReady) {}
       (void)hipGetLastError();
-    } else if (!(sync_env && sync_env[0] == '0')) {
+    } else if (h->sw.setmodel_sync) {
       BBH_HIP_TRY(h, hipStreamSynchronize(s));
     }
     sm_stamp("synced");
@@ -745,10 +742,10 @@ static int bbh_chol_and_alpha(bbh_handle* h, double jitter, int* info_out, doubl
   int info = 0;
   BBH_HIP_TRY(h, hipMemcpyAsync(&info, h->d_info, sizeof(int), hipMemcpyDeviceToHost, s));
   BBH_HIP_TRY(h, hipStreamSynchronize(s));
-  if (info == -7 && h->potrf_tiles) {  // tile-dataflow launch gave up: redo with the per-step path
-    if (getenv("BBH_TILE_TRACE")) fprintf(stderr, "bbh_chol_and_alpha: tile-dataflow launch gave up (np = %lld, spin limit %d)\n", (long long)h->np, h->tile_spin_limit);
-    h->potrf_tiles = false;
-    if (h->tile_spin_limit >= 1024) bbh_potrf_tiles_mark_unusable(h->device);
+  if (info == -7 && h->sw.potrf_tiles && !h->tiles_gave_up) {  // tile-dataflow launch gave up: redo with the per-step path
+    if (h->sw.tile_trace) fprintf(stderr, "bbh_chol_and_alpha: tile-dataflow launch gave up (np = %lld, spin limit %d)\n", (long long)h->np, h->sw.tile_spin_limit);
+    h->tiles_gave_up = true;
+    if (h->sw.tile_spin_limit >= 1024) bbh_potrf_tiles_mark_unusable(h->device);
     return bbh_chol_and_alpha(h, jitter, info_out, jitter_latent);
   }
   *info_out = info;
@@ -765,10 +762,11 @@ static int bbh_fit_enqueue(bbh_handle* h) {
     h->last_fit_form = BBH_FIT_FORM_RFF;
     return bbh_rff_fit_enqueue(h);
   }
+  const int fit_flow = h->flow_gave_up ? 0 : h->sw.fit_flow;  // (a dataflow launch that gave up ends the form for this handle)
   {  // small models: the whole evaluation in one workgroup (bbh_linalg.hip), reading theta from and writing the results to the
      // pinned staging buffers themselves - one launch, no copies
     void *th_dev = nullptr, *out_dev = nullptr, *info_dev = nullptr;
-    if (h->fit_small && h->np == 64 && hipHostGetDevicePointer(&th_dev, h->pin_theta, 0) == hipSuccess &&
+    if (h->sw.fit_small && h->np == 64 && hipHostGetDevicePointer(&th_dev, h->pin_theta, 0) == hipSuccess &&
         hipHostGetDevicePointer(&out_dev, h->pin_out, 0) == hipSuccess && hipHostGetDevicePointer(&info_dev, h->pin_info, 0) == hipSuccess &&
         bbh_fit_small_launch(h, 0.0, (const double*)th_dev, (double*)out_dev, (int*)info_dev)) {
       h->last_fit_form = BBH_FIT_FORM_SMALL;
@@ -782,12 +780,12 @@ static int bbh_fit_enqueue(bbh_handle* h) {
     // factorisation of the two-launch default needs all its tiles co-resident, which ends at 16 block rows on 256 CUs; the ticketed
     // roles of the one-launch form have no such requirement (launch by launch an evaluation at np = 1088 was 1.36 ms against 0.46 ms
     // at np = 1024: profiles/r06_fit_eval_beyond_1024.log)
-    const bool one_launch = (h->fit_flow == 2 || h->fit_flow == 3) ? h->np <= 1024 : (h->fit_flow == 1 && h->np > 1024 && bbh_fit_flow_eligible(h));
+    const bool one_launch = (fit_flow == 2 || fit_flow == 3) ? h->np <= 1024 : (fit_flow == 1 && h->np > 1024 && bbh_fit_flow_eligible(h));
     if (one_launch && h->np > 64 && hipHostGetDevicePointer(&th_dev, h->pin_theta, 0) == hipSuccess &&
         hipHostGetDevicePointer(&out_dev, h->pin_out, 0) == hipSuccess && hipHostGetDevicePointer(&info_dev, h->pin_info, 0) == hipSuccess) {
       *h->pin_info = -99;  // (sentinel: the kernel's last role writes the flag; a launch that gave up never does)
       // (theta as kernel arguments when it fits: ~250 workgroups fetching it from the host-mapped buffer is the slower way)
-      const bool split = h->fit_flow == 3 && h->np <= 1024;
+      const bool split = fit_flow == 3 && h->np <= 1024;
       if (bbh_fit_flow_launch(h, tl <= 52 ? nullptr : (const double*)th_dev, (double*)out_dev, (int*)info_dev, false, h->pin_theta, split)) {
         h->flow_in_flight = true;
         h->last_fit_form = split ? BBH_FIT_FORM_SPLIT : BBH_FIT_FORM_ONE_LAUNCH;
@@ -799,21 +797,20 @@ static int bbh_fit_enqueue(bbh_handle* h) {
   {  // default for 64 < np <= 1024, zero copies: the tile-dataflow factorisation builds its Gram tiles itself, the dataflow tail reads the
      // factor - theta from, results into the host-mapped staging buffers (two launches)
     void *th_dev = nullptr, *out_dev = nullptr, *info_dev = nullptr;
-    if (h->fit_flow == 1 && h->np <= 1024 && h->tile_gram && bbh_fit_flow_eligible(h) && hipHostGetDevicePointer(&th_dev, h->pin_theta, 0) == hipSuccess &&
+    if (fit_flow == 1 && h->np <= 1024 && h->sw.tile_gram && bbh_fit_flow_eligible(h) && hipHostGetDevicePointer(&th_dev, h->pin_theta, 0) == hipSuccess &&
         hipHostGetDevicePointer(&out_dev, h->pin_out, 0) == hipSuccess && hipHostGetDevicePointer(&info_dev, h->pin_info, 0) == hipSuccess) {
       // (theta through one H2D copy, not read from the host-mapped buffer by every workgroup: ~100 workgroups fetching it over the
       // host link at the same moment took 30 us - profiles/r05_tile_gram.log)
       // theta travels as kernel arguments of the two launches (<= 49 doubles): no copy in the stream, and no workgroup reads it from
       // the host-mapped buffer (BBH_TILE_GRAM_THETA=copy: one H2D copy and device reads, the A/B form)
-      const char* th_env = getenv("BBH_TILE_GRAM_THETA");
-      const bool by_value = !(th_env && th_env[0] == 'c') && tl <= 52;
+      const bool by_value = !h->sw.tile_gram_theta_copy && tl <= 52;
       const double* th_src = by_value ? nullptr : h->d_theta;
       if (!by_value) BBH_HIP_TRY(h, hipMemcpyAsync(h->d_theta, h->pin_theta, sizeof(double) * tl, hipMemcpyHostToDevice, s));
       // K^-1's tiles ride in the factorisation launch where its workgroups and theirs are co-resident (n <= 832): they follow the rows of
       // L^-1 as these appear, and the launch behind it starts at alpha
       alignas(16) unsigned char mt_buf[128];
       static_assert(sizeof(mt_buf) >= 96, "pd_mt_args");
-      const bool want_mt = h->tile_mt && bbh_fit_flow_mt_args(h, mt_buf);
+      const bool want_mt = h->sw.tile_mt && bbh_fit_flow_mt_args(h, mt_buf);
       h->skip_x_memset = true;
       const bool tiles = bbh_potrf_trtri_from_inputs(h, th_src, h->pin_theta, want_mt ? mt_buf : nullptr);
       h->skip_x_memset = false;
@@ -839,7 +836,7 @@ static int bbh_fit_enqueue(bbh_handle* h) {
      // (LOO: q, Q), value, gradient pairs, their sums - as ONE dataflow launch writing the results into the pinned buffers
      // (7-10 kernels, a memset and two copies before)
     void *out_dev = nullptr, *info_dev = nullptr;
-    if (h->fit_flow == 1 && h->np <= 1024 && bbh_fit_flow_eligible(h) && hipHostGetDevicePointer(&out_dev, h->pin_out, 0) == hipSuccess &&
+    if (fit_flow == 1 && h->np <= 1024 && bbh_fit_flow_eligible(h) && hipHostGetDevicePointer(&out_dev, h->pin_out, 0) == hipSuccess &&
         hipHostGetDevicePointer(&info_dev, h->pin_info, 0) == hipSuccess) {
       bbh_launch_gram(h, 0.0, 0.0);
       h->skip_x_memset = true;  // (the tail reads the lower tiles of L^-1 only)
@@ -948,7 +945,7 @@ extern "C" int bbh_fit_value_grad(bbh_handle* h, const double* theta_host, doubl
     BBH_HIP_TRY(h, hipHostMalloc((void**)&h->pin_info, sizeof(int), hipHostMallocDefault));
   }
   memcpy(h->pin_theta, theta_host, sizeof(double) * tl);
-  if (h->fit_graph_mode && !h->fit_exec && !h->fit_graph_failed && bbh_fit_graph_build(h) != 0) h->fit_graph_failed = true;
+  if (h->sw.fit_graph_mode && !h->fit_exec && !h->fit_graph_failed && bbh_fit_graph_build(h) != 0) h->fit_graph_failed = true;
   hipStream_t s = h->stream;
   if (h->fit_exec) {
     BBH_HIP_TRY(h, hipStreamSynchronize(h->stream));  // earlier work on the handle's stream (normally idle here)
@@ -960,7 +957,7 @@ extern "C" int bbh_fit_value_grad(bbh_handle* h, const double* theta_host, doubl
   }
   const auto t_enq = std::chrono::steady_clock::now();
   BBH_HIP_TRY(h, hipStreamSynchronize(s));
-  if (getenv("BBH_FIT_TRACE")) {  // host time spent enqueueing vs waiting for the device
+  if (h->sw.fit_trace) {  // host time spent enqueueing vs waiting for the device
     const auto t_end = std::chrono::steady_clock::now();
     fprintf(stderr, "bbh_fit_value_grad (%s): enqueue %.1f us, wait %.1f us\n", h->fit_exec ? "graph" : "launches",
             std::chrono::duration<double, std::micro>(t_enq - t_begin).count(),
@@ -971,15 +968,15 @@ extern "C" int bbh_fit_value_grad(bbh_handle* h, const double* theta_host, doubl
     h->info_clean = *h->pin_info != -99;  // (the tail's last role copied the Cholesky flag out and reset it)
     if (*h->pin_info == -99) {  // the dataflow launch never reported: one of its waits ran out of polls - launch path from now on
       // (a reported -7 is the tile-dataflow FACTORISATION in front of it giving up: handled below, the dataflow tail stays in use)
-      if (getenv("BBH_TILE_TRACE")) fprintf(stderr, "bbh_fit_value_grad: one-launch evaluation gave up (np = %lld, flag %d)\n", (long long)h->np, *h->pin_info);
+      if (h->sw.tile_trace) fprintf(stderr, "bbh_fit_value_grad: one-launch evaluation gave up (np = %lld, flag %d)\n", (long long)h->np, *h->pin_info);
       bbh_fit_flow_reset(h);
       return bbh_fit_value_grad(h, theta_host, value_host, grad_host);
     }
   }
-  if (*h->pin_info == -7 && h->potrf_tiles) {  // the tile-dataflow launch gave up (workgroups not co-resident): per-step path
-    if (getenv("BBH_TILE_TRACE")) fprintf(stderr, "bbh_fit_value_grad: tile-dataflow launch gave up (np = %lld, spin limit %d)\n", (long long)h->np, h->tile_spin_limit);
-    h->potrf_tiles = false;
-    if (h->tile_spin_limit >= 1024) bbh_potrf_tiles_mark_unusable(h->device);  // (not when a test forced the give-up with a tiny poll budget)
+  if (*h->pin_info == -7 && h->sw.potrf_tiles && !h->tiles_gave_up) {  // the tile-dataflow launch gave up (workgroups not co-resident): per-step path
+    if (h->sw.tile_trace) fprintf(stderr, "bbh_fit_value_grad: tile-dataflow launch gave up (np = %lld, spin limit %d)\n", (long long)h->np, h->sw.tile_spin_limit);
+    h->tiles_gave_up = true;
+    if (h->sw.tile_spin_limit >= 1024) bbh_potrf_tiles_mark_unusable(h->device);  // (not when a test forced the give-up with a tiny poll budget)
     if (h->fit_exec) {
       hipGraphExecDestroy(h->fit_exec);
       h->fit_exec = nullptr;

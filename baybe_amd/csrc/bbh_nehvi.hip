@@ -349,14 +349,9 @@ extern "C" int bbh_cells_build_dev(bbh_handle* h, const double* Fb_dev, int64_t 
   BBH_HIP_TRY(h, hipMemcpyAsync(st->d_ref, ref_host, sizeof(double) * m, hipMemcpyHostToDevice, s));
   BBH_HIP_TRY(h, hipMemsetAsync(st->d_cnt + S, 0, sizeof(int), s));
   dim3 grid((unsigned)S), block(64);
-  // hipFuncSetAttribute is per DEVICE (a process-wide flag left a second GPU of the same process without the raised limit)
 #define NV_LAUNCH(MM)                                                                                                                \
   {                                                                                                                                  \
-    static bool attr_set[64] = {};                                                                                                   \
-    if (!attr_set[h->device & 63]) {                                                                                                 \
-      BBH_HIP_TRY(h, hipFuncSetAttribute((const void*)bbh_cells_kernel<MM>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_limit)); \
-      attr_set[h->device & 63] = true;                                                                                               \
-    }                                                                                                                                \
+    BBH_HIP_TRY(h, bbh_allow_lds(h->device, (const void*)bbh_cells_kernel<MM>, (size_t)lds_limit));                                   \
     hipLaunchKernelGGL(bbh_cells_kernel<MM>, grid, block, lds, s, Fb_dev, (int)nb, st->d_ref, cap, st->d_slots, st->d_cnt, st->d_cnt + S); \
   }
   switch (m) {

@@ -206,7 +206,7 @@ static int bbh_coopg_kd(const bbh_handle* h) {
 }
 
 static bool bbh_coopg_model(const bbh_handle* h) {
-  if (!bbh_materialised_only(h) || h->coop_mode <= 0 || !h->use_pipeline) return false;
+  if (!bbh_materialised_only(h) || h->sw.coop_mode <= 0 || !h->sw.use_pipeline) return false;
   if (h->nb > 4 * BBH_COOP_ROUNDS || h->nb % 4 != 0) return false;
   const bbh_kern_spec ks = bbh_kern_spec_of(h);
   for (int f = 0; f < ks.F; f++)
@@ -353,7 +353,7 @@ int bbh_pack_operands(bbh_handle* h) {
   }
   // ---- register-resident small-model form (n <= 128): the lower triangle of L^-T as fragments, bbh_small.h ----
   h->small_nb = 0;
-  if (h->small_on && h->use_pipeline && nb <= 8 && h->n >= 1) {
+  if (h->sw.small_on && h->sw.use_pipeline && nb <= 8 && h->n >= 1) {
     const int NB = (int)((h->n + 15) / 16);
     const bool has_tbl0 = (T > 1) || h->desc.use_outputscale;
     if (bbh_small_launch(h->kd, h->desc.kernel_kind, has_tbl0, NB, 0, h->num_cu, nullptr, SmallArgs{})) {
@@ -366,8 +366,8 @@ int bbh_pack_operands(bbh_handle* h) {
   h->coop_ready = false;
   {
     const bool has_tbl0 = (T > 1) || h->desc.use_outputscale;
-    if (h->coop_mode > 0 && h->use_pipeline && nb <= 4 * BBH_COOP_ROUNDS && nb % 4 == 0 &&
-        bbh_coop_launch(h->kd, h->desc.kernel_kind, has_tbl0, dim3(0), 0, nullptr, CoopArgs{})) {
+    if (h->sw.coop_mode > 0 && h->sw.use_pipeline && nb <= 4 * BBH_COOP_ROUNDS && nb % 4 == 0 &&
+        bbh_coop_launch(h->kd, h->desc.kernel_kind, has_tbl0, dim3(0), 0, nullptr, CoopArgs{}, h->sw.coop_small)) {
       const int g0 = BBH_COOP_ROUNDS - (int)(nb / 4);
       const int64_t frags = coop_frags_before(BBH_COOP_ROUNDS) - coop_frags_before(g0);
       if (!h->d_rstream || h->rstream_frags != frags) {
@@ -424,7 +424,7 @@ int bbh_pack_operands(bbh_handle* h) {
   h->coop2_ready = false;
   {
     const bool has_tbl0 = (T > 1) || h->desc.use_outputscale;
-    if (h->coop_mode > 0 && h->use_pipeline && nb > 4 * BBH_COOP_ROUNDS && nb <= 8 * BBH_COOP_ROUNDS && nb % 4 == 0 &&
+    if (h->sw.coop_mode > 0 && h->sw.use_pipeline && nb > 4 * BBH_COOP_ROUNDS && nb <= 8 * BBH_COOP_ROUNDS && nb % 4 == 0 &&
         bbh_coop2_launch(h->kd, h->desc.kernel_kind, has_tbl0, dim3(0), 0, nullptr, CoopArgs{})) {
       const int g0 = 2 * BBH_COOP_ROUNDS - (int)(nb / 4);
       const int64_t frags = coop2_frags(g0);
@@ -469,18 +469,10 @@ int bbh_pack_operands(bbh_handle* h) {
   return 0;
 }
 
-int bbh_launch_fused(bbh_handle* h, const double* X_dev, int64_t N, int64_t ldx, double* mean_dev, double* var_dev,
-                     double* cross_dev, bool with_var) {
-  if (N <= 0) return 0;
-  if (bbh_is_rff(h)) return bbh_rff_posterior_launch(h, X_dev, N, ldx, mean_dev, with_var ? var_dev : nullptr, cross_dev);
-  // composite / RQ / piecewise kernels: the cooperative form with the generic production for variance passes without pending
-  // columns (bbh_coopg.h), otherwise the materialised-K* path (fused qLogEI: applied by the caller)
-  const bool coopg = h->coopg_ready && with_var && h->p == 0 && !cross_dev && !h->fuse_qz && h->use_mean_valu;
-  // ... and their mean-only / cross-covariance passes (steps >= 2 of a greedy batch) on bbh_coopg_cross_kernel (BBH_COOPG_CROSS=0: A/B)
-  const bool coopg_cross = h->coopg_ready && !with_var && !h->fuse_qz && h->coopg_cross_on;
-  if (bbh_materialised_only(h) && !coopg && !coopg_cross)
-    return bbh_launch_unfused_ext(h, X_dev, N, ldx, mean_dev, with_var ? var_dev : nullptr, cross_dev);
-  FusedArgs a;
+// What every fused-posterior launch passes: the model's operands and constants, no outputs, no pending columns, no fused epilogue,
+// no kernel-value cache.  (has_tbl, mean_valu, nl: set by the callers whose kernels read them.)
+static void bbh_fill_fused_args(bbh_handle* h, FusedArgs& a, const double* X_dev, int64_t N, int64_t ldx) {
+  a.numcol_identity = 0;
   a.X = X_dev;
   a.N = N;
   a.ldx = ldx;
@@ -493,9 +485,9 @@ int bbh_launch_fused(bbh_handle* h, const double* X_dev, int64_t N, int64_t ldx,
   a.tasktbl = h->d_tasktbl;
   a.taskmean = h->hadamard ? h->d_theta + bbh_hadamard_offset(h) + h->T : nullptr;
   a.taskext = h->d_taskext;
-  a.mean = mean_dev;
-  a.var = var_dev;
-  a.cross = cross_dev;
+  a.mean = nullptr;
+  a.var = nullptr;
+  a.cross = nullptr;
   a.pass_off = h->d_pass_off;
   a.pass_w = h->d_pass_w;
   a.npass = h->npass;
@@ -503,11 +495,11 @@ int bbh_launch_fused(bbh_handle* h, const double* X_dev, int64_t N, int64_t ldx,
   a.dn = h->dn;
   a.kd = h->kd;
   a.nb = (int)h->nb;
-  a.nb_ext = (int)h->nb_ext;
+  a.nb_ext = (int)h->nb;
   a.task_col = h->desc.task_col;
   a.T = h->T;
-  a.p = h->p;
-  a.with_var = with_var ? 1 : 0;
+  a.p = 0;
+  a.with_var = 0;
   a.ybar = h->ybar;
   a.ysd = h->ysd;
   a.mean_const = h->theta[1];
@@ -518,6 +510,33 @@ int bbh_launch_fused(bbh_handle* h, const double* X_dev, int64_t N, int64_t ldx,
   a.q_sign = 1.0;
   a.q_alive = nullptr;
   a.q_scores = nullptr;
+  a.kvcache = nullptr;
+  a.slab_flags = nullptr;
+  a.nslab = 0;
+  a.nxcc = 1;
+  a.ncache = 0;
+  a.nblk = (N + 63) / 64;
+}
+
+int bbh_launch_fused(bbh_handle* h, const double* X_dev, int64_t N, int64_t ldx, double* mean_dev, double* var_dev,
+                     double* cross_dev, bool with_var) {
+  if (N <= 0) return 0;
+  if (bbh_is_rff(h)) return bbh_rff_posterior_launch(h, X_dev, N, ldx, mean_dev, with_var ? var_dev : nullptr, cross_dev);
+  // composite / RQ / piecewise kernels: the cooperative form with the generic production for variance passes without pending
+  // columns (bbh_coopg.h), otherwise the materialised-K* path (fused qLogEI: applied by the caller)
+  const bool coopg = h->coopg_ready && with_var && h->p == 0 && !cross_dev && !h->fuse_qz && h->sw.use_mean_valu;
+  // ... and their mean-only / cross-covariance passes (steps >= 2 of a greedy batch) on bbh_coopg_cross_kernel (BBH_COOPG_CROSS=0: A/B)
+  const bool coopg_cross = h->coopg_ready && !with_var && !h->fuse_qz && h->sw.coopg_cross_on;
+  if (bbh_materialised_only(h) && !coopg && !coopg_cross)
+    return bbh_launch_unfused_ext(h, X_dev, N, ldx, mean_dev, with_var ? var_dev : nullptr, cross_dev);
+  FusedArgs a;
+  bbh_fill_fused_args(h, a, X_dev, N, ldx);
+  a.mean = mean_dev;
+  a.var = var_dev;
+  a.cross = cross_dev;
+  a.nb_ext = (int)h->nb_ext;
+  a.p = h->p;
+  a.with_var = with_var ? 1 : 0;
   if (h->fuse_qz && with_var) {  // set by bbh_score_qlogei for this launch only
     a.qz = h->fuse_qz;
     a.qS = h->fuse_S;
@@ -537,19 +556,13 @@ int bbh_launch_fused(bbh_handle* h, const double* X_dev, int64_t N, int64_t ldx,
   a.numcol_identity = 1;
   for (int j = 0; j < h->dn; j++)
     if (h->numcol[j] != j) a.numcol_identity = 0;
-  const int kdp = ((m52 || ((rbf || m32) && !has_tbl)) && h->use_pipeline && (h->kd == 2 || h->kd == 4 || h->kd == 6 || h->kd == 8 || h->kd == 12 || h->kd == 16)) ? h->kd : 0;
-  a.nblk = (N + 63) / 64;
+  const int kdp = ((m52 || ((rbf || m32) && !has_tbl)) && h->sw.use_pipeline && (h->kd == 2 || h->kd == 4 || h->kd == 6 || h->kd == 8 || h->kd == 12 || h->kd == 16)) ? h->kd : 0;
   dim3 grid((unsigned)a.nblk), block(256);
   // alpha in LDS costs 8 n bytes: beyond n = 4096 it would crowd out the candidate fragments / the cache
-  a.mean_valu = (kdp && h->p == 0 && !cross_dev && h->use_mean_valu && h->nb <= 256) ? 1 : 0;
+  a.mean_valu = (kdp && h->p == 0 && !cross_dev && h->sw.use_mean_valu && h->nb <= 256) ? 1 : 0;
   size_t lds = sizeof(double) * (4 * h->kd * 64 + (a.qz ? a.qS : 0) + (a.mean_valu ? 16 * h->nb : 0));
-  a.kvcache = nullptr;
-  a.ncache = 0;
   a.nl = 0;
-  a.slab_flags = nullptr;
-  a.nslab = 0;
-  a.nxcc = 1;
-  if (kdp && with_var && h->npass > 1 && h->use_kvcache) {
+  if (kdp && with_var && h->npass > 1 && h->sw.use_kvcache) {
     // Kernel-value cache for the k-blocks left of the last pass.  As many of them as fit next to the other
     // LDS users without costing the second workgroup per CU (half of the CU's LDS per workgroup) stay in
     // wave-private LDS (2 KB per k-block and wave); the rest goes to slabs in global memory claimed per wave.
@@ -557,13 +570,13 @@ int bbh_launch_fused(bbh_handle* h, const double* X_dev, int64_t N, int64_t ldx,
     const size_t lds_wg = h->lds_per_block / 2;  // two workgroups per CU
     const size_t budget = lds_wg > lds ? lds_wg - lds : 0;
     int nl = (int)(budget / (4 * 256 * sizeof(double)));
-    if (h->kv_lds_blocks >= 0 && nl > h->kv_lds_blocks) nl = h->kv_lds_blocks;
+    if (h->sw.kv_lds_blocks >= 0 && nl > h->sw.kv_lds_blocks) nl = h->sw.kv_lds_blocks;
     a.nl = nl < a.ncache ? nl : a.ncache;
     // The k-blocks that do not fit LDS go to global slabs only when there are many of them (n >= ~768:
     // -5 % at n = 1024, -2.5 % at n = 2048); for a few (n = 512: 8 blocks) recomputing them is as fast as
     // streaming them through the fabric (5.17 vs 5.18 ms) and moves 4 GB less per launch.
     const int rest = a.ncache - a.nl;
-    const bool global_part = h->kv_global_mode == 1 || (h->kv_global_mode < 0 && rest >= 24);
+    const bool global_part = h->sw.kv_global_mode == 1 || (h->sw.kv_global_mode < 0 && rest >= 24);
     if (!global_part) a.ncache = a.nl;
     lds += sizeof(double) * 4 * 256 * (size_t)a.nl;
   }
@@ -629,11 +642,9 @@ int bbh_launch_fused(bbh_handle* h, const double* X_dev, int64_t N, int64_t ldx,
   // Register-resident form (n <= 128, variance pass without pending columns): persistent waves, the model in registers / LDS
   // (64 < n <= 128: the operand fragments are 45 - 74 KB of LDS that every workgroup fills first - ahead of the cooperative form
   // only once the candidate set amortises that: measured cross-overs, profiles/r04_ab_small_form.log; BBH_SMALL_FORCE=1 lifts the rule)
-  const char* sf_env = getenv("BBH_SMALL_FORCE");
-  const bool small_force = sf_env && sf_env[0] == '1';
   const int64_t small_min_rows[9] = {0, 0, 0, 0, 0, 20000, 60000, 120000, 300000};
-  if (h->small_nb > 0 && h->small_on && with_var && h->p == 0 && !cross_dev && !a.qz && h->use_mean_valu &&
-      (small_force || N >= small_min_rows[h->small_nb])) {
+  if (h->small_nb > 0 && h->sw.small_on && with_var && h->p == 0 && !cross_dev && !a.qz && h->sw.use_mean_valu &&
+      (h->sw.small_force || N >= small_min_rows[h->small_nb])) {
     SmallArgs sa;
     sa.f = a;
     sa.rsmall = h->d_rsmall;
@@ -651,12 +662,11 @@ int bbh_launch_fused(bbh_handle* h, const double* X_dev, int64_t N, int64_t ldx,
   // below; for small candidate sets its four waves per tile cut the latency to a third (0.016 vs 0.052 ms for 1000 rows).
   // (round 3, profiles/r03_ab_small_n.log: with the hoisted set-up loads the cooperative form is level or ahead for every
   // n <= 256 and candidate count from 1e4 to 1e6 - its 16-candidate workgroups quantise the tail of a launch four times finer)
-  const bool coop_pays = true;
   // (its own instantiation set: also RBF with a task table - the multi-task HVARFNER / BOTORCH presets - which the
   // windowed pipelined form does not have)
-  const int kdc = (h->use_pipeline && (h->kd == 2 || h->kd == 4 || h->kd == 6 || h->kd == 8 || h->kd == 12 || h->kd == 16)) ? h->kd : 0;
-  const bool coop_mean_valu = h->p == 0 && !cross_dev && h->use_mean_valu && h->nb <= 256;
-  if (h->coop_ready && coop_pays && kdc && with_var && coop_mean_valu && !a.qz) {
+  const int kdc = (h->sw.use_pipeline && (h->kd == 2 || h->kd == 4 || h->kd == 6 || h->kd == 8 || h->kd == 12 || h->kd == 16)) ? h->kd : 0;
+  const bool coop_mean_valu = h->p == 0 && !cross_dev && h->sw.use_mean_valu && h->nb <= 256;
+  if (h->coop_ready && kdc && with_var && coop_mean_valu && !a.qz) {
     CoopArgs ca;
     ca.f = a;
     ca.rstream = h->d_rstream;
@@ -668,7 +678,7 @@ int bbh_launch_fused(bbh_handle* h, const double* X_dev, int64_t N, int64_t ldx,
     // template parameter.)
     const size_t clds = sizeof(double) * (16 * (size_t)h->nb + (2 * 4 * 256 + 128));
     const dim3 cgrid((unsigned)((N + 15) / 16));
-    bbh_coop_launch(kdc, a.kind, has_tbl, cgrid, clds, h->stream, ca);
+    bbh_coop_launch(kdc, a.kind, has_tbl, cgrid, clds, h->stream, ca, h->sw.coop_small);
     h->last_form = 1;
     BBH_HIP_TRY(h, hipGetLastError());
     return 0;
@@ -1547,53 +1557,6 @@ static int bbh_nehvi_samples_impl(bbh_handle* h, const double* z_host, const dou
   return 0;
 }
 
-static void bbh_fill_fused_args(bbh_handle* h, FusedArgs& a, const double* X_dev, int64_t N, int64_t ldx) {
-  a.numcol_identity = 0;
-  a.X = X_dev;
-  a.N = N;
-  a.ldx = ldx;
-  a.trainfrag = h->d_trainfrag;
-  a.rfrag = h->d_rfrag;
-  a.meanB = h->d_meanB;
-  a.scl = h->d_sclofs;
-  a.ofs = h->d_sclofs + h->dn;
-  a.numcol = h->d_numcol;
-  a.tasktbl = h->d_tasktbl;
-  a.taskmean = h->hadamard ? h->d_theta + bbh_hadamard_offset(h) + h->T : nullptr;
-  a.taskext = h->d_taskext;
-  a.mean = nullptr;
-  a.var = nullptr;
-  a.cross = nullptr;
-  a.pass_off = h->d_pass_off;
-  a.pass_w = h->d_pass_w;
-  a.npass = h->npass;
-  a.kind = h->desc.kernel_kind;
-  a.dn = h->dn;
-  a.kd = h->kd;
-  a.nb = (int)h->nb;
-  a.nb_ext = (int)h->nb;
-  a.task_col = h->desc.task_col;
-  a.T = h->T;
-  a.p = 0;
-  a.with_var = 0;
-  a.ybar = h->ybar;
-  a.ysd = h->ysd;
-  a.mean_const = h->theta[1];
-  a.prior_scale = h->desc.use_outputscale ? h->theta[2] : 1.0;
-  a.qz = nullptr;
-  a.qS = 0;
-  a.q_best_f = 0.0;
-  a.q_sign = 1.0;
-  a.q_alive = nullptr;
-  a.q_scores = nullptr;
-  a.kvcache = nullptr;
-  a.slab_flags = nullptr;
-  a.nslab = 0;
-  a.nxcc = 1;
-  a.ncache = 0;
-  a.nblk = (N + 63) / 64;
-}
-
 // tmat[i][c] = ybar + ysd * (mean_const(task of i) + P[i][c]) for the real columns of a padded product P [Nc, spad]
 __global__ void bbh_columns_affine_kernel(const double* __restrict__ P, int64_t spad, int64_t Nc, int64_t S,
                                           const double* __restrict__ X, int64_t ldx, const double* __restrict__ theta,
@@ -1662,13 +1625,11 @@ static int bbh_posterior_columns_impl(bbh_handle* h, const double* X_dev, int64_
   const int64_t S = h->ncols, spad = bbh_round_up(S, 128), groups = spad / 128;
   const int64_t nks = h->np / 4;
   const int64_t str_c = sample_major ? 1 : S, str_s = sample_major ? N : 1;
-  const char* cc_env = getenv("BBH_COLUMNS_COOP");  // A/B switch: 0 keeps the plain kernel for every column group
-  const bool coop_cols = !(cc_env && cc_env[0] == '0');
+  const bool coop_cols = h->sw.columns_coop;  // (A/B switch: false keeps the plain kernel for every column group)
   int64_t g = 0;
   // super-groups of (up to) four column groups on the cooperative kernel while at least three remain (with fewer, three of its
   // four waves would only produce kernel values: the plain kernel's four tiles per workgroup are the better use of the CU)
-  const char* nt_env = getenv("BBH_COLUMNS_NT");
-  const int cnt = nt_env ? atoi(nt_env) : 2;
+  const int cnt = h->sw.columns_nt;
   for (; coop_cols && groups - g >= 3; g += 4) {
     auto launch = [&](auto nt, auto sm) {
       constexpr int NT = decltype(nt)::value;

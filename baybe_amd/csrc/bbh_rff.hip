@@ -370,8 +370,7 @@ int bbh_rff_setup(bbh_handle* h) {
   BBH_HIP_TRY(h, hipMemcpy(st->d_W, Wp.data(), sizeof(double) * Wp.size(), hipMemcpyHostToDevice));
   BBH_HIP_TRY(h, hipMemcpy(st->d_lo, lo3.data(), sizeof(double) * lo3.size(), hipMemcpyHostToDevice));
   BBH_HIP_TRY(h, hipMemset(st->d_E, 0, sizeof(double) * mp * 16));
-  // (per device and cheap: set whenever a model is set up, not once per process)
-  BBH_HIP_TRY(h, hipFuncSetAttribute((const void*)bbh_rff_solve_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(double) * 4 * 64 * PD_LD)));
+  BBH_HIP_TRY(h, bbh_allow_lds(h->device, (const void*)bbh_rff_solve_kernel, sizeof(double) * 4 * 64 * PD_LD));
   return st->Dh <= 64 ? rff_posterior_lds_attr(h, st->Dh) : 0;
 }
 
@@ -583,8 +582,7 @@ __global__ __launch_bounds__(DH == 64 ? 256 : 512) __attribute__((amdgpu_waves_p
 
 static int rff_posterior_lds_attr(bbh_handle* h, int Dh) {
   const void* fn = Dh == 64 ? (const void*)bbh_rff_posterior_kernel<64> : (const void*)bbh_rff_posterior_kernel<32>;
-  BBH_HIP_TRY(h, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)(sizeof(double) * ((size_t)rff_qp_elems(Dh / 8) + 2 * Dh * 16 + RFF_MAXDN * (Dh + 3)))));
+  BBH_HIP_TRY(h, bbh_allow_lds(h->device, fn, sizeof(double) * ((size_t)rff_qp_elems(Dh / 8) + 2 * Dh * 16 + RFF_MAXDN * (Dh + 3))));
   return 0;
 }
 

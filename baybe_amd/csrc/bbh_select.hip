@@ -484,8 +484,7 @@ static int sel_ensure(bbh_handle* h, bbh_select_state* st) {
   BBH_HIP_TRY(h, hipMalloc((void**)&st->d_out_i, sizeof(int64_t) * 64));
   // results straight to the host: the select kernel's stores travel over the link, one stream synchronisation ends the step
   // (BBH_SELECT_MAPPED=0: device buffer + copy, for A/B)
-  const char* mp = getenv("BBH_SELECT_MAPPED");
-  if (mp && mp[0] == '0') {
+  if (!h->sw.select_mapped) {
     st->h_res = nullptr;
   } else if (hipHostMalloc(&st->h_res, 16 + 64 * 16, hipHostMallocMapped) == hipSuccess) {
     if (hipHostGetDevicePointer(&st->h_res_dev, st->h_res, 0) != hipSuccess) {
@@ -560,7 +559,7 @@ int bbh_argmax_rounds(bbh_handle* h, const double* scores_dev, int64_t N, double
 
 // k best scores on the device: *vals_dev / *idx_dev point into the handle's selection state (valid until its next use)
 int bbh_topk_device(bbh_handle* h, const double* scores_dev, int64_t N, int64_t k, double** vals_dev, int64_t** idx_dev) {
-  if (!h->select_on) return bbh_topk_rounds_device(h, scores_dev, N, k, vals_dev, idx_dev);
+  if (!h->sw.select_on) return bbh_topk_rounds_device(h, scores_dev, N, k, vals_dev, idx_dev);
   int rc = sel_check(h, scores_dev, N, k);
   if (rc) return rc;
   BBH_HIP_TRY(h, hipSetDevice(h->device));
@@ -575,7 +574,7 @@ extern "C" int bbh_topk(bbh_handle* h, const double* scores_dev, int64_t N, int6
     h->err = "bbh_topk: bad arguments (1 <= k <= min(N, 64))";
     return -1;
   }
-  if (!h->select_on) return bbh_topk_rounds(h, scores_dev, N, k, vals_host, idx_host);
+  if (!h->sw.select_on) return bbh_topk_rounds(h, scores_dev, N, k, vals_host, idx_host);
   int rc = sel_check(h, scores_dev, N, k);
   if (rc) return rc;
   BBH_HIP_TRY(h, hipSetDevice(h->device));
@@ -590,7 +589,7 @@ extern "C" int bbh_argmax(bbh_handle* h, const double* scores_dev, int64_t N, do
     h->err = "bbh_argmax: bad arguments";
     return -1;
   }
-  if (!h->select_on) return bbh_argmax_rounds(h, scores_dev, N, best_val_host, best_idx_host);
+  if (!h->sw.select_on) return bbh_argmax_rounds(h, scores_dev, N, best_val_host, best_idx_host);
   return bbh_topk(h, scores_dev, N, 1, best_val_host, best_idx_host);
 }
 
@@ -661,11 +660,11 @@ extern "C" int bbh_qlogei_q1_topk(bbh_handle* h, const double* mean_dev, const d
   if (rc) return rc;
   BBH_HIP_TRY(h, hipSetDevice(h->device));
   bbh_select_state* st = sel_state(h);
-  rc = (h->q1_sliced && h->select_on) ? bbh_qlogei_q1_sliced(h, mean_dev, var_dev, N, z_host, S, best_f, sign, alive_dev, scores_dev) : 1;
+  rc = (h->sw.q1_sliced && h->sw.select_on) ? bbh_qlogei_q1_sliced(h, mean_dev, var_dev, N, z_host, S, best_f, sign, alive_dev, scores_dev) : 1;
   if (rc < 0) return rc;
   if (rc == 1) {  // one thread per candidate, then the keys in their own pass
     if ((rc = bbh_qlogei_q1_rounds(h, mean_dev, var_dev, N, z_host, S, best_f, sign, alive_dev, scores_dev))) return rc;
-    if (!h->select_on) return bbh_topk_rounds(h, scores_dev, N, k, vals_host, idx_host);
+    if (!h->sw.select_on) return bbh_topk_rounds(h, scores_dev, N, k, vals_host, idx_host);
     if ((rc = sel_ensure(h, st)) || (rc = sel_keys(h, st, scores_dev, N))) return rc;
   }
   return sel_finish(h, st, scores_dev, N, k, vals_host, idx_host, nullptr, nullptr);

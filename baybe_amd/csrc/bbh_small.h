@@ -217,12 +217,15 @@ __host__ inline size_t small_lds_bytes(int kd, int NB) {
 // executed at the memory side across the 8 XCDs: 0.8 ms per 1e6 candidates whatever n is; dropped.)
 template <int KD, int KVF, int NB>
 static void small_go(int64_t tiles, int num_cu, hipStream_t s, const SmallArgs& a) {
-  static int per_cu = 0;
+  static int per_cu_dev[64];  // workgroups per CU, per device
   const size_t lds = small_lds_bytes(KD, NB);
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  int& per_cu = per_cu_dev[dev & 63];
+  (void)bbh_allow_lds(dev, (const void*)bbh_small_posterior_kernel<KD, KVF, NB>, lds);
   if (!per_cu) {
     int n = 0;
     constexpr int NT = small_threads(NB);
-    if (lds > 64 * 1024) hipFuncSetAttribute((const void*)bbh_small_posterior_kernel<KD, KVF, NB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, bbh_small_posterior_kernel<KD, KVF, NB>, NT, lds) != hipSuccess || n < 1) n = 1;
     per_cu = n > 5 ? n - 1 : n;  // (beyond the SGPR bound's reach the API may over-report by one)
   }

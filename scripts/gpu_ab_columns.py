@@ -21,19 +21,26 @@ def timeit(fn, reps=10):
     return e0.elapsed_time(e1) / reps
 
 
-def case(name, g, X, n, S_list):
+def case(name, fitted, spec, Xt, y, X, n, S_list):
     Xd = torch.from_numpy(X).cuda()
     rng = np.random.default_rng(3)
+    gs = {}
+    for mode in ("0", "1", "2"):  # one handle per variant (a handle reads its switches when it is created), same model and parameters
+        os.environ["BBH_COLUMNS_COOP"] = "0" if mode == "0" else "1"
+        os.environ["BBH_COLUMNS_NT"] = "2" if mode == "2" else "1"
+        gs[mode] = g = engine.HipGP(0)
+        g.set_model(spec, Xt, y)
+        g.factorize(fitted.params)
+    os.environ.pop("BBH_COLUMNS_COOP"); os.environ.pop("BBH_COLUMNS_NT")
+    g = fitted
     for S in S_list:
-        g.set_mean_columns(rng.standard_normal((n, S)))
+        Y = rng.standard_normal((n, S))
         out = {}
-        for mode in ("0", "1", "2"):
-            os.environ["BBH_COLUMNS_COOP"] = "0" if mode == "0" else "1"
-            os.environ["BBH_COLUMNS_NT"] = "2" if mode == "2" else "1"
+        for mode, gm in gs.items():
+            gm.set_mean_columns(Y)
             for sm in (False, True):
-                ms = timeit(lambda: g.posterior_columns(Xd, sample_major=sm))
-                out[(mode, sm)] = (ms, g.posterior_columns(Xd, sample_major=sm).cpu().numpy())
-        os.environ.pop("BBH_COLUMNS_COOP"); os.environ.pop("BBH_COLUMNS_NT")
+                ms = timeit(lambda: gm.posterior_columns(Xd, sample_major=sm))
+                out[(mode, sm)] = (ms, gm.posterior_columns(Xd, sample_major=sm).cpu().numpy())
         for sm in (False, True):
             assert np.array_equal(out[("0", sm)][1], out[("1", sm)][1]) and np.array_equal(out[("0", sm)][1], out[("2", sm)][1]), (name, S, sm)
         flops = 2.0 * X.shape[0] * S * (16 * g_nb(g))
@@ -41,6 +48,8 @@ def case(name, g, X, n, S_list):
               f"cooperative {out[('1', True)][0]:.3f} ms ({flops / out[('1', True)][0] / 1e9:.1f} TF/s)  two tiles "
               f"{out[('2', True)][0]:.3f} ms ({flops / out[('2', True)][0] / 1e9:.1f} TF/s)   [candidate-major: "
               f"{out[('0', False)][0]:.3f} / {out[('1', False)][0]:.3f} / {out[('2', False)][0]:.3f} ms]  outputs bitwise equal", flush=True)
+    for gm in gs.values():
+        gm.close()
 
 
 def g_nb(g):
@@ -54,9 +63,9 @@ for n in (287, 128, 512):
     y = -((Xt - 0.3) ** 2).sum(1)
     spec = gp_spec.GPSpec.baybe_default(d, np.zeros(d), np.ones(d))
     g = engine.HipGP(0); g.set_model(spec, Xt, y); g.fit(maxiter=20)
-    case("plain", g, X, n, (512, 384, 128, 1000) if n == 287 else (512,))
+    case("plain", g, spec, Xt, y, X, n, (512, 384, 128, 1000) if n == 287 else (512,))
     g.close()
 Xtl, Xt, y = make_tl_problem(N, 8, 64, T=4, seed=5)
 spec = gp_spec.GPSpec.baybe_default(9, np.zeros(9), np.ones(9), task_idx=8, n_tasks=4)
 g = engine.HipGP(0); g.set_model(spec, Xt, y); g.fit(maxiter=10)
-case("icm", g, Xtl, len(y), (512,))
+case("icm", g, spec, Xt, y, Xtl, len(y), (512,))

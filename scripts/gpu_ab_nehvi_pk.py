@@ -18,12 +18,24 @@ for yo in ys:
     g = engine.HipGP(0); g.set_model(gp_spec.GPSpec.baybe_default(d, np.zeros(d), np.ones(d)), Xt, np.asarray(yo)); g.fit(maxiter=30); engines.append(g)
 ref = compute_ref_point(np.stack([np.asarray(v) for v in ys], 1))
 Xd = torch.from_numpy(X).cuda()
-for S in (512, 128):
-    hv = HipNEHVI(engines, np.ones(m), Xt, ref, n_mc_samples=S, prune_baseline=True)
+
+
+def prepared(S, **env):
+    """A HipNEHVI whose handles are created under ``env`` (a handle reads its BBH_* switches when it is created)."""
+    os.environ.update(env)
+    try:
+        hv = HipNEHVI(engines, np.ones(m), Xt, ref, n_mc_samples=S, prune_baseline=True)
+    finally:
+        for k in env:
+            os.environ.pop(k)
     hv.prepare(1234, prune_seed=99)
+    return hv
+
+
+for S in (512, 128):
     out = {}
     for mode in ("0", "1"):
-        os.environ["BBH_NEHVI_PK"] = mode
+        hv = prepared(S, BBH_NEHVI_PK=mode)
         sc = hv.score(Xd); torch.cuda.synchronize()
         for o in hv.outputs: o.ext.timing(True)
         for o in hv.outputs: o.ext.timing_read(True, "nehvi")
@@ -32,8 +44,7 @@ for S in (512, 128):
         tot = [o.ext.timing_read(True, "nehvi") for o in hv.outputs]
         ms, cnt = sum(t[0] for t in tot), sum(t[1] for t in tot)
         out[mode] = (ms / max(cnt, 1), sc.cpu().numpy())
-    os.environ.pop("BBH_NEHVI_PK")
-    os.environ["BBH_NEHVI_LOG"] = "1"; slog = hv.score(Xd).cpu().numpy(); os.environ.pop("BBH_NEHVI_LOG")
+    slog = prepared(S, BBH_NEHVI_LOG="1").score(Xd).cpu().numpy()
     a, b = out["0"][1], out["1"][1]
     fin = np.isfinite(a) & np.isfinite(b)
     dev = np.abs(a - b)[fin]

@@ -9,8 +9,8 @@ from bench import synth_problem
 from baybe_amd import engine, gp_spec
 
 
-def handle(flag, d, Xt, y):
-    os.environ["BBH_COOP"] = flag
+def handle(flag, small, d, Xt, y):
+    os.environ["BBH_COOP"], os.environ["BBH_COOP_SMALL"] = flag, small  # (a handle reads its switches when it is created)
     g = engine.HipGP(0)
     g.set_model(gp_spec.GPSpec.baybe_default(d, np.zeros(d), np.ones(d)), Xt, y)
     g.factorize(gp_spec.GPParams(np.full(d, math.exp(math.sqrt(2) - 3) * math.sqrt(d)), math.exp(-5.0), 0.0))
@@ -20,22 +20,20 @@ def handle(flag, d, Xt, y):
 
 for (d, n) in ((15, 256), (15, 192), (15, 128), (10, 64), (6, 32)):
     Xall, Xt, y = synth_problem(1_000_000, d, n, 0)
-    gs = {f: handle(f, d, Xt, y) for f in ("0", "2")}
+    variants = (("0", "1"), ("2", "0"), ("2", "1"))  # (BBH_COOP, BBH_COOP_SMALL): windowed, eight-round coop, four-round coop
+    gs = {v: handle(*v, d, Xt, y) for v in variants}
     for N in (10_000, 30_000, 100_000, 200_000, 400_000, 1_000_000):
         Xd = torch.from_numpy(Xall[:N]).cuda()
         t = {}
-        variants = (("0", "1"), ("2", "0"), ("2", "1"))  # (handle, BBH_COOP_SMALL): windowed, eight-round coop, four-round coop
-        for f, sm in variants:
-            os.environ["BBH_COOP_SMALL"] = sm
-            for _ in range(3): gs[f].posterior(Xd)
-            torch.cuda.synchronize(); gs[f].timing_read(reset=True)
+        for v in variants:
+            for _ in range(3): gs[v].posterior(Xd)
+            torch.cuda.synchronize(); gs[v].timing_read(reset=True)
         for rnd in range(3):
-            for f, sm in variants:
-                os.environ["BBH_COOP_SMALL"] = sm
-                for _ in range(10): gs[f].posterior(Xd)
+            for v in variants:
+                for _ in range(10): gs[v].posterior(Xd)
                 torch.cuda.synchronize()
-                ms, cnt = gs[f].timing_read(reset=True)
-                t.setdefault((f, sm), []).append(ms / cnt)
+                ms, cnt = gs[v].timing_read(reset=True)
+                t.setdefault(v, []).append(ms / cnt)
         fl = N * (n * n + 2 * n * d + 16 * n)
         a, b, c = (np.median(t[v]) for v in variants)
         print(f"d={d} n={n} N={N}: windowed {a*1e3:.1f} us ({fl / (a * 1e-3) / 78.6e12:.3f})  cooperative 8 rounds {b*1e3:.1f} us ({fl / (b * 1e-3) / 78.6e12:.3f})"

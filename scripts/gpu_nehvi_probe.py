@@ -23,14 +23,25 @@ for o in range(m):
     models.append(go.fit_gp(oracle_spec(spec), Xt, Y[:, o], params=go.GPParams(fi.params.lengthscale, fi.params.noise, fi.params.mean)))
 signs = np.ones(m); ref = compute_ref_point(Y)
 Xd = torch.from_numpy(X).cuda()
-for S in (512, 128):
-    hv = HipNEHVI(engines, signs, Xt, ref, n_mc_samples=S, prune_baseline=True)
+
+
+def prepared(S, **env):
+    """A HipNEHVI whose handles are created under ``env`` (a handle reads its BBH_* switches when it is created)."""
+    os.environ.update(env)
+    try:
+        hv = HipNEHVI(engines, signs, Xt, ref, n_mc_samples=S, prune_baseline=True)
+    finally:
+        for k in env:
+            os.environ.pop(k)
     hv.prepare(1234, prune_seed=99)
-    os.environ.pop("BBH_NEHVI_LOG", None)
+    return hv
+
+
+os.environ.pop("BBH_NEHVI_LOG", None)
+for S in (512, 128):
+    hv = prepared(S)
     s_lin = hv.score(Xd).cpu().numpy()
-    os.environ["BBH_NEHVI_LOG"] = "1"
-    s_log = hv.score(Xd).cpu().numpy()
-    os.environ.pop("BBH_NEHVI_LOG", None)
+    s_log = prepared(S, BBH_NEHVI_LOG="1").score(Xd).cpu().numpy()
     keep = no.prune_baseline(models, signs, Xt, ref, 99)
     orc = no.NEHVIOracle(models, signs, Xt[keep], ref, no.sobol_normal_base_samples_nd(S, len(keep) + 1, m, 1234))
     top = np.argsort(-s_lin, kind="stable")[:12]

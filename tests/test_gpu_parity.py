@@ -1059,12 +1059,20 @@ def test_joint_batches_beyond_sixteen_points(gp):
     m, v = gp.posterior(Xl)
     cr = gp.cross_cov_many(Xl, P21)
     alive = torch.from_numpy((rng.random(3003) > 0.1).astype(np.uint8)).to(m.device)
-    one = _np(gp.qlogei_pending_big(m, v, cr, P21, z, gp.best_f(1.0), alive=alive))
+    stats, best_f = gp.posterior_joint(P21), gp.best_f(1.0)
+    one = _np(gp.qlogei_pending_big(m, v, cr, P21, z, best_f, alive=alive, stats=stats))
+    # (a handle reads its switches when it is created: the many-chunk run is a second handle's, on the same model, theta and inputs)
     os.environ["BBH_QBIG_WS_MB"] = "1"
     try:
-        many_chunks = _np(gp.qlogei_pending_big(m, v, cr, P21, z, gp.best_f(1.0), alive=alive))
+        g2 = engine.HipGP(0)
     finally:
         del os.environ["BBH_QBIG_WS_MB"]
+    try:
+        g2.set_model(spec, Xt, y)
+        g2.factorize(fi.params)
+        many_chunks = _np(g2.qlogei_pending_big(m, v, cr, P21, z, best_f, alive=alive, stats=stats))
+    finally:
+        g2.close()
     assert np.array_equal(one, many_chunks) and np.isfinite(one[_np(alive).astype(bool)]).all() and np.isneginf(one[~_np(alive).astype(bool)]).all()
     with pytest.raises(ValueError):
         gp.greedy_qlogei(X, 5, S=64, seed=1, X_pending=X[:62])  # 62 + 4 picks > 63 pending points
