@@ -53,7 +53,7 @@ MAX_PENDING_BIG = 63  # joint q'-batches through bbh_qlogei_pending_big: q' = 1 
 MAX_RFF_SAMPLES = 256  # RFFKernel(num_samples): frequencies of the feature-space model (csrc/bbh_rff.hip: m = 2 D <= 512)
 MAX_OBJECTIVES = 4
 TIMED_FAMILIES = {"posterior": 0, "cross": 1, "pending": 2, "columns": 3, "nehvi": 4, "q1": 5, "select": 6}  # enum bbh_timed_family
-ACQ_KINDS = {"qLogEI": 0, "qEI": 1, "qPI": 2, "qSR": 3, "qUCB": 4, "qPSTD": 5,
+ACQ_KINDS = {"qLogEI": 0, "qEI": 1, "qPI": 2, "qSR": 3, "qUCB": 4, "qPSTD": 5, "qNEI": 6, "qLogNEI": 7,
              "PM": 10, "PSTD": 11, "UCB": 12, "EI": 13, "LogEI": 14, "PI": 15}
 
 # name -> (restype, argtypes); every symbol include/baybe_hip.h declares
@@ -141,6 +141,12 @@ SIGNATURES = {
     ),
     "bbh_pareto_frequency": (C.c_int, [C.c_void_p, c_double_p, C.c_int64, C.c_int64, C.c_int32, c_double_p, c_int64_p]),
     "bbh_pareto_frequency_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, c_double_p, c_int64_p]),
+    "bbh_best_frequency_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, c_int64_p]),
+    "bbh_sample_best_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    "bbh_nei_q1": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, c_double_p, C.c_int64, C.c_void_p, C.c_double,
+                             C.c_void_p, C.c_void_p]),
+    "bbh_score_nei": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, c_double_p, C.c_int64, C.c_void_p,
+                                C.c_double, C.c_void_p, C.c_void_p]),
     "bbh_nehvi_samples": (C.c_int, [C.c_void_p, c_double_p, C.c_int64, C.c_int64, C.c_double, C.c_int32, C.c_int32, C.c_void_p, C.c_int32]),
     "bbh_nehvi_samples_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_double, C.c_int32, C.c_int32,
                                         C.c_void_p, C.c_int32]),
@@ -170,6 +176,7 @@ SIGNATURES = {
         [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, c_double_p, c_int64_p, c_double_p],
     ),
     "bbh_last_posterior_form": (C.c_int, [C.c_void_p]),
+    "bbh_last_nei_form": (C.c_int, [C.c_void_p]),
     "bbh_last_fit_form": (C.c_int, [C.c_void_p]),
     "bbh_timing_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "bbh_timing_read": (C.c_int, [C.c_void_p, c_double_p, c_int64_p, C.c_int]),

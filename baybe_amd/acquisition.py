@@ -1,7 +1,7 @@
 """Declarative acquisition functions of the HIP path (mirror of ``baybe/acquisition/acqfs.py``).
 
-Only what the hot path scores on the device is defined: qLogEI (``acqfs.py:219-223``) and the
-closed-form/posterior read-backs built from (mean, variance).  BoTorch's defaults that BayBE
+Only what the hot path scores on the device is defined: qLogEI (``acqfs.py:219-223``), the noisy forms qNEI / qLogNEI
+(``acqfs.py:226-243``), qLogNEHVI and the closed-form/posterior read-backs built from (mean, variance).  BoTorch's defaults that BayBE
 does not expose are recorded as explicit fields (sample count 512; fat=True, tau_relu=1e-6,
 tau_max=1e-2 are compiled into the kernels)."""
 
@@ -121,13 +121,39 @@ class qLogNoisyExpectedHypervolumeImprovement:
 qLogNEHVI = qLogNoisyExpectedHypervolumeImprovement
 
 
+def _nei_class(name: str, abbr: str, doc: str):
+    """Declarative noisy expected improvement (``acqfs.py:226-243``), scored by ``baybe_amd.nei.HipNEI``."""
+    ns = {
+        "__doc__": doc, "abbreviation": abbr, "kind": abbr, "supports_batching": True, "supports_pending_experiments": True,
+        "supports_multi_output": False, "is_mc": True, "is_analytic": False,
+        "__annotations__": {"abbreviation": ClassVar[str], "kind": ClassVar[str], "supports_batching": ClassVar[bool],
+                            "supports_pending_experiments": ClassVar[bool], "supports_multi_output": ClassVar[bool],
+                            "is_mc": ClassVar[bool], "is_analytic": ClassVar[bool], "prune_baseline": bool, "n_mc_samples": int},
+        # Auto-prune baseline points that are unlikely to be the best of any joint posterior sample (prune_inferior_points).
+        "prune_baseline": field(default=True, validator=instance_of(bool)),
+        # Sobol base samples (BoTorch default for single-output MC acquisition functions; BayBE has no knob for it).
+        "n_mc_samples": field(default=512, validator=[instance_of(int), ge(1)]),
+    }
+    return define(frozen=True)(type(name, (), ns))
+
+
+qNoisyExpectedImprovement = _nei_class("qNoisyExpectedImprovement", "qNEI", "Monte Carlo based noisy expected improvement.")
+qLogNoisyExpectedImprovement = _nei_class("qLogNoisyExpectedImprovement", "qLogNEI",
+                                          "Logarithmic Monte Carlo based noisy expected improvement.")
+qNEI, qLogNEI = qNoisyExpectedImprovement, qLogNoisyExpectedImprovement
+_NOISY_EI = {c.abbreviation: c for c in (qNoisyExpectedImprovement, qLogNoisyExpectedImprovement)}
+
+
 def convert_acqf(acqf):
     """``baybe.acquisition.utils.convert_acqf``: accept abbreviations / BayBE objects."""
     if acqf is None or isinstance(acqf, (qLogExpectedImprovement, qLogNoisyExpectedHypervolumeImprovement)):
         return acqf
-    if type(acqf) in _SINGLE_OUTPUT.values():
+    if type(acqf) in _SINGLE_OUTPUT.values() or type(acqf) in _NOISY_EI.values():
         return acqf
     name = acqf if isinstance(acqf, str) else type(acqf).__name__
+    for abbr, cls in _NOISY_EI.items():
+        if name in (abbr, cls.__name__):
+            return cls() if isinstance(acqf, str) else cls(prune_baseline=getattr(acqf, "prune_baseline", True))
     for abbr, cls in _SINGLE_OUTPUT.items():
         if name in (abbr, cls.__name__):
             kw = {}
@@ -146,5 +172,5 @@ def convert_acqf(acqf):
     from baybe_amd.exceptions import IncompatibleAcquisitionFunctionError
 
     raise IncompatibleAcquisitionFunctionError(
-        f"The HIP recommender scores the MC / analytic EI-PI-UCB-SR families and qLogNEHVI on the device; '{name}' is not available on this path."
+        f"The HIP recommender scores the MC / analytic EI-PI-UCB-SR families, qNEI / qLogNEI and qLogNEHVI on the device; '{name}' is not available on this path."
     )

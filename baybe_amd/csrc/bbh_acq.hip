@@ -12,8 +12,8 @@
 #include <algorithm>
 
 #include "bbh_common.h"
+#include "bbh_acqmath.h"  // TAU_RELU, bbh_fatplus_core, bbh_safe_sd
 
-#define TAU_RELU 1e-6
 #define TAU_MAX 1e-2
 #define LOG_TAU_RELU -13.815510557964274  // log(1e-6)
 #ifndef BBH_PENDING_LSE
@@ -26,40 +26,6 @@ typedef float bbh_f2 __attribute__((ext_vector_type(2)));
 #ifndef BBH_PENDING_FAST
 #define BBH_PENDING_FAST 1  // joint q'-batch qLogEI kernels: reduced-precision logarithms where the power tau_max = 0.01 absorbs them
 #endif
-
-// fatplus(x; tau) / tau = softplus(t) + 0.1 / (1 + t^2),  t = x / tau; torch softplus threshold 20
-template <int NEWTON = 2>
-__device__ __forceinline__ double bbh_fatplus_core(double t) {
-  // softplus: t / tau_relu is huge in magnitude for almost every sample, so the log1p(exp) branch is rare.
-  // It is entered through a wave-uniform test (ballot): a per-lane branch in unrolled callers is
-  // if-converted by the compiler into "always evaluate both sides", i.e. ~50 extra VALU per call.
-  double sp = (t > 20.0) ? t : 0.0;
-  const bool mid = !(t > 20.0) && !(t < -750.0);
-  if (__builtin_amdgcn_ballot_w64(mid) != 0) {
-    if (mid) sp = log1p(exp(t));
-  }
-  // 0.1 / (1 + t^2) without the IEEE division sequence (div_scale / div_fmas / div_fixup, ~15 VALU
-  // of the ~22 per sample): v_rcp_f64 seed (2^-26) and two Newton steps; 1 + t^2 is in [1, 1e40) for
-  // every reachable t, so no scaling is needed.  Relative error <= 2 ulp.
-  const double d = fma(t, t, 1.0);
-  double y = __builtin_amdgcn_rcp(d);
-  y = fma(fma(-d, y, 1.0), y, y);
-  if (NEWTON > 1) y = fma(fma(-d, y, 1.0), y, y);  // (one step: <= 2^-46 relative - enough where the caller's own terms are single precision)
-  y = (d < INFINITY) ? y : 0.0;  // |t| = inf (unbounded cell): the Newton step would produce inf * 0
-  return fma(0.1, y, sp);
-}
-
-// 1x1 psd_safe_cholesky: v <= 0 (or NaN) -> add jitter 1e-8, 1e-7, 1e-6
-__device__ __forceinline__ double bbh_safe_sd(double v) {
-  if (!(v > 0.0)) {
-    v += 1e-8;
-    if (!(v > 0.0)) {
-      v += 1e-7;
-      if (!(v > 0.0)) v += 1e-6;
-    }
-  }
-  return sqrt(fmax(v, 0.0));
-}
 
 // q' = 1:  score = log( mean_s fatplus(sign (mu + sd z_s) - best_f) )
 //               = logmeanexp_s log_fatplus(...)   (all terms positive, no cancellation)

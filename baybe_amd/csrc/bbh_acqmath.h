@@ -1,0 +1,62 @@
+// Per-sample building blocks shared by the acquisition kernels (bbh_acq.hip, bbh_nei.hip, the scoring epilogue of
+// bbh_coopcols.h): the fat softplus of qLogEI-type utilities and the 1 x 1 psd_safe_cholesky.  Maths restated in
+// oracle/gp_oracle.py (log_fatplus, _safe_sqrt_var).
+#pragma once
+#include <math.h>
+
+#include "bbh_common.h"
+
+#define TAU_RELU 1e-6
+
+// fatplus(x; tau) / tau = softplus(t) + 0.1 / (1 + t^2),  t = x / tau; torch softplus threshold 20
+template <int NEWTON = 2>
+__device__ __forceinline__ double bbh_fatplus_core(double t) {
+  // softplus: t / tau_relu is huge in magnitude for almost every sample, so the log1p(exp) branch is rare.
+  // It is entered through a wave-uniform test (ballot): a per-lane branch in unrolled callers is
+  // if-converted by the compiler into "always evaluate both sides", i.e. ~50 extra VALU per call.
+  double sp = (t > 20.0) ? t : 0.0;
+  const bool mid = !(t > 20.0) && !(t < -750.0);
+  if (__builtin_amdgcn_ballot_w64(mid) != 0) {
+    if (mid) sp = log1p(exp(t));
+  }
+  // 0.1 / (1 + t^2) without the IEEE division sequence (div_scale / div_fmas / div_fixup, ~15 VALU
+  // of the ~22 per sample): v_rcp_f64 seed (2^-26) and two Newton steps; 1 + t^2 is in [1, 1e40) for
+  // every reachable t, so no scaling is needed.  Relative error <= 2 ulp.
+  const double d = fma(t, t, 1.0);
+  double y = __builtin_amdgcn_rcp(d);
+  y = fma(fma(-d, y, 1.0), y, y);
+  if (NEWTON > 1) y = fma(fma(-d, y, 1.0), y, y);  // (one step: <= 2^-46 relative - enough where the caller's own terms are single precision)
+  y = (d < INFINITY) ? y : 0.0;  // |t| = inf (unbounded cell): the Newton step would produce inf * 0
+  return fma(0.1, y, sp);
+}
+
+// 1x1 psd_safe_cholesky: v <= 0 (or NaN) -> add jitter 1e-8, 1e-7, 1e-6
+__device__ __forceinline__ double bbh_safe_sd(double v) {
+  if (!(v > 0.0)) {
+    v += 1e-8;
+    if (!(v > 0.0)) {
+      v += 1e-7;
+      if (!(v > 0.0)) v += 1e-6;
+    }
+  }
+  return sqrt(fmax(v, 0.0));
+}
+
+// ---- qNEI / qLogNEI (bbh_nei.hip) ----------------------------------------------------------------
+// One MC sample of a candidate: the joint draw f_s = E[f(x) | D, F_b,s] + sd z_x,s against the sample's best baseline
+// value, u_s = sign f_s - best_s.  LOG: fatplus(u_s; tau_relu) / tau_relu (summed in the linear domain like
+// bbh_qlogei_q1_kernel: the terms lie in [1e-17 / u_s^2, |u_s| / tau], no scaling is needed for any reachable u_s);
+// otherwise max(u_s, 0).  The fused epilogue and the unfused verification kernel both call this, so their terms are equal
+// bit for bit and only the order of the sums differs.
+template <bool LOG>
+__device__ __forceinline__ double bbh_nei_term(double cond_mean, double sd, double zx, double best, double sign) {
+  const double u = sign * fma(sd, zx, cond_mean) - best;
+  if constexpr (LOG) return bbh_fatplus_core<2>(u * (1.0 / TAU_RELU));
+  return fmax(u, 0.0);
+}
+// sum over the S samples -> score
+template <bool LOG>
+__device__ __forceinline__ double bbh_nei_finish(double sum, int S) {
+  if constexpr (LOG) return log(TAU_RELU) + log(sum) - log((double)S);
+  return sum / (double)S;
+}

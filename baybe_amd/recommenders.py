@@ -246,18 +246,27 @@ class HipRecommenderImpl:
                                    n_mc_samples=acqf.n_mc_samples, prune_baseline=acqf.prune_baseline,
                                    device=models[0].engine.device)
             self._best_f = None
+        elif acqf.kind in ("qNEI", "qLogNEI"):
+            from baybe_amd.nei import HipNEI
+
+            # the noisy forms have no incumbent value: the baseline (all training inputs, _builder.py:319-324) is sampled instead
+            X_base = np.ascontiguousarray(searchspace.transform(measurements, allow_extra=True).to_numpy(dtype=np.float64))
+            self._nehvi = HipNEI(surrogate.engine, surrogate.sign, X_base, n_mc_samples=acqf.n_mc_samples,
+                                 prune_baseline=acqf.prune_baseline, log=acqf.kind == "qLogNEI", device=surrogate.engine.device)
+            self._best_f = None
         else:
             self._best_f = surrogate.engine.best_f(surrogate.sign)  # _builder.py:141-161, 256-265
         return surrogate, acqf
 
     def _check_batch_size(self, batch_size, pending_experiments=None) -> None:
         """The joint q'-batch kernels hold 1 + (pending + earlier picks) <= 16 points; the reference has no such
-        limit, so say so before any candidate is scored (single-target MC acquisition functions only: qLogNEHVI
-        caches picks into its baseline and analytic functions have q = 1)."""
+        limit, so say so before any candidate is scored (single-target MC acquisition functions only: qLogNEHVI and
+        qNEI / qLogNEI cache picks into their baseline and analytic functions have q = 1)."""
         n_pend = len(self._pending_comp) if self._pending_comp is not None else (
             0 if pending_experiments is None else len(pending_experiments))
         acqf = self._acqf_in_use
-        if acqf is not None and (acqf.supports_multi_output or getattr(acqf, "is_analytic", False)):
+        if acqf is not None and (acqf.supports_multi_output or getattr(acqf, "is_analytic", False)
+                                 or getattr(acqf, "kind", None) in ("qNEI", "qLogNEI")):
             return
         # qLogEI: up to 64 points (beyond 16 through bbh_qlogei_pending_big, the factor in a global workspace); the other MC
         # acquisition functions: 16
@@ -453,7 +462,7 @@ class HipRecommenderImpl:
         _check_continuous_part(cont)
         acqf, surrogate = self._acqf_in_use, self._surrogate_model
         if self._nehvi is not None:
-            raise IncompatibilityError("Multi-output objectives in hybrid / continuous spaces are not on the HIP path; use BotorchRecommender.")
+            raise IncompatibilityError("Multi-output objectives and qNEI / qLogNEI in hybrid / continuous spaces are not on the HIP path; use BotorchRecommender.")
         if batch_size > 1 and not acqf.supports_batching:
             raise IncompatibleAcquisitionFunctionError(
                 f"The '{self.__class__.__name__}' only works with Monte Carlo acquisition functions for batch sizes > 1.")

@@ -24,6 +24,10 @@
  *   bbh_set_mean_columns /   f(X_baseline), cached Cholesky root)
  *   bbh_posterior_columns(_sm)
  *   bbh_qlognehvi(_sm)       qLogNoisyExpectedHypervolumeImprovement     baybe/acquisition/acqfs.py:477-484
+ *   bbh_score_nei /          qNoisyExpectedImprovement and               baybe/acquisition/acqfs.py:226-243;
+ *   bbh_nei_q1 /             qLogNoisyExpectedImprovement, q' = 1, with  baybe/acquisition/_builder.py:319-324 (X_baseline,
+ *   bbh_sample_best_dev /    prune_inferior_points                       prune_baseline)
+ *   bbh_best_frequency_dev
  *
  * Conventions
  *  - extern "C"; every function returns 0 on success, <0 on error;
@@ -240,7 +244,8 @@ int bbh_qlogei_pending(bbh_handle* h, const double* mean_dev, const double* var_
 /* ---- the other acquisition functions of acqfs.py:161-290 on the same inputs ----------- */
 enum bbh_acq_kind {
   BBH_ACQ_QLOGEI = 0, BBH_ACQ_QEI = 1, BBH_ACQ_QPI = 2, BBH_ACQ_QSR = 3, BBH_ACQ_QUCB = 4, BBH_ACQ_QPSTD = 5,
-  BBH_ACQ_PM = 10, BBH_ACQ_PSTD = 11, BBH_ACQ_UCB = 12, BBH_ACQ_EI = 13, BBH_ACQ_LOGEI = 14, BBH_ACQ_PI = 15
+  BBH_ACQ_PM = 10, BBH_ACQ_PSTD = 11, BBH_ACQ_UCB = 12, BBH_ACQ_EI = 13, BBH_ACQ_LOGEI = 14, BBH_ACQ_PI = 15,
+  BBH_ACQ_QNEI = 6, BBH_ACQ_QLOGNEI = 7 /* noisy expected improvement: scored by bbh_score_nei / bbh_nei_q1 only */
 };
 /* MC family, q'=1 and q'=1+p (mean_s max_j u(obj_sj); qPI tau = 1e-3; qUCB/qPSTD use the sample mean). */
 int bbh_mc_acq_q1(bbh_handle* h, int32_t kind, const double* mean_dev, const double* var_dev, int64_t N,
@@ -323,6 +328,32 @@ int bbh_cells_read_dev(bbh_handle* h, int64_t* off_host, double* lo_host, double
 int bbh_qlognehvi_cells(bbh_handle* h, int32_t m, int64_t N, const double* const* tmat_dev,
                         const double* const* var_dev, const double* sign_host, const double* zx_host, int64_t S,
                         const uint8_t* alive_dev, double* scores_dev);
+
+/* ---- qNoisyExpectedImprovement / qLogNoisyExpectedImprovement (baybe/acquisition/acqfs.py:226-243) -------------------------
+ * BoTorch's qNoisyExpectedImprovement / qLogNoisyExpectedImprovement as BayBE builds them (X_baseline = all training inputs,
+ * prune_baseline, cache_root: baybe/acquisition/_builder.py:319-324), q' = 1; picks and pending points join the baseline
+ * (set_X_pending with a cached root).  The set-up is qLogNEHVI's with one target: h holds the model extended by the nb baseline
+ * rows, bbh_nehvi_samples(h, ..., m = 1, want_columns = 1) wrote the oriented baseline samples obj_dev [S, nb] and installed the
+ * S weight columns.  Per candidate and sample:  f_s = E[f(x) | D, F_b,s] + safe_sd(Var[f(x) | D, X_b]) zx[s],
+ * u_s = sign f_s - best[s];  BBH_ACQ_QLOGNEI: logmeanexp_s log_fatplus(u_s; 1e-6),  BBH_ACQ_QNEI: mean_s max(u_s, 0);
+ * rows with alive_dev[i] == 0 score -inf. */
+/* prune_inferior_points (botorch, called from the acquisition constructor): counts_host[b] = number of the S samples whose largest
+ * value is point b's (ties: the first index).  Returns after the stream has drained. */
+int bbh_best_frequency_dev(bbh_handle* h, const double* obj_dev, int64_t S, int64_t nb, int64_t* counts_host);
+/* best_dev[s] = max_b obj_dev[s, b]: the per-sample incumbent of the noisy improvement.  Asynchronous. */
+int bbh_sample_best_dev(bbh_handle* h, const double* obj_dev, int64_t S, int64_t nb, double* best_dev);
+/* Unfused form over a materialised sample-major block tmat_sm_dev [S, N] (bbh_posterior_columns_sm of the same handle):
+ * verification form, models on the materialised-K* columns path, S > 512.  var_dev / alive_dev / scores_dev [N]; the caller
+ * chunks the candidates.  Asynchronous. */
+int bbh_nei_q1(bbh_handle* h, int32_t kind, const double* tmat_sm_dev, const double* var_dev, int64_t N, const double* zx_host,
+               int64_t S, const double* best_dev, double sign, const uint8_t* alive_dev, double* scores_dev);
+/* Fused form: the cooperative conditional-mean kernel with a scoring epilogue - candidates X_dev [N, ldx] in, scores out, the
+ * [S, N] matrix of conditional means is never written and no workspace is taken.  S must be the installed column count.
+ * Returns 0 when the pass is enqueued and 1 when the form does not apply (S > 512, a model on the materialised-K* path, or
+ * BBH_NEI_FUSED=0): nothing is enqueued then and the caller takes bbh_posterior_columns_sm + bbh_nei_q1. */
+int bbh_score_nei(bbh_handle* h, int32_t kind, const double* X_dev, int64_t N, int64_t ldx, const double* var_dev,
+                  const double* zx_host, int64_t S, const double* best_dev, double sign, const uint8_t* alive_dev,
+                  double* scores_dev);
 
 /* Box decomposition of the non-dominated region, one per MC sample (host code, no device work; BoTorch's
  * FastNondominatedPartitioning inside qLogNoisyExpectedHypervolumeImprovement, built at
@@ -411,6 +442,9 @@ int bbh_timing_read(bbh_handle* h, double* fused_ms_total, int64_t* fused_launch
  * Polynomial, Periodic: bbh_coopg_posterior_kernel), 5 = register- / LDS-resident (n <= 128, bbh_small_posterior_kernel),
  * 6 = feature space (BBH_KERNEL_RFF: bbh_rff_posterior_kernel), -1 = none yet. */
 int bbh_last_posterior_form(bbh_handle* h);
+/* Form the last qNEI / qLogNEI scoring pass of this handle ran as: 1 = fused (bbh_score_nei), 2 = unfused (bbh_nei_q1),
+ * -1 = none yet. */
+int bbh_last_nei_form(bbh_handle* h);
 /* Form the last fit evaluation (bbh_fit_value_grad) of this handle ran as, i.e. the path that produced the returned value and gradient
  * (after a give-up of a dataflow launch: the path that redid the evaluation), -1 = none yet. */
 enum bbh_fit_form {
