@@ -194,8 +194,11 @@ __device__ __forceinline__ double bbh_fast_log_pos(double x) {
 // factor (Q (Q + 1) / 2 doubles) and the per-sample values live in registers (every index is a
 // compile-time constant), the base samples z [S, Q] in LDS (broadcast reads).  The LDS form needs 69 KB
 // per 64 threads - one wave per two SIMDs - and took 30 ms per greedy step on 1e6 candidates, six times the
-// fused posterior; this one runs 256-thread workgroups at full occupancy.  The arithmetic (operation order
-// included) is that of the LDS form, so both give bit-identical scores.
+// fused posterior; this one runs 256-thread workgroups at full occupancy.  The factorisation (operation order
+// included) is that of the LDS form; the per-sample arithmetic is not since the reduced-precision fat maximum and the
+// linear-domain sum below: the two forms agree to 2.1e-9 in the score over tests/test_joint_batch_gpu.py (Q = 2, 7, 14 under
+// BBH_PENDING_LDS=1 and the 60 KB hand-over at Q = 14), the LDS form within 3e-11 of the oracle and this one within 2.1e-9
+// (tolerance 1e-8; profiles/joint_batch_observed_deviations.json).
 // SAMPLE SLICES (gridDim.y > 1, linear-domain form only): blockIdx.y takes the samples [y per, (y + 1) per) and writes the partial sum
 // of its terms to partial[y][i]; bbh_pending_finish_kernel adds the slices in a fixed order and takes the logarithm.  With one
 // thread per candidate a 1e5-row candidate set is 1563 wavefronts, 1.5 per SIMD, each one long dependent chain: the slices bring
