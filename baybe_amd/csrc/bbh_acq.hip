@@ -5,20 +5,24 @@
 // base samples shared by all candidates; objective = sign * sample (minimisation = -1,
 // baybe/objectives/base.py:99-105).  Maths restated in oracle/gp_oracle.py (log_fatplus, fatmax,
 // logmeanexp, psd_safe_cholesky jitter).
+//
+// The kernels that score a candidate jointly with p pending points (bbh_qlogei_pending_q_kernel, bbh_qlogei_pending_kernel,
+// bbh_qlogei_pending_big_kernel, bbh_mc_pending_q_kernel, bbh_mc_pending_kernel) share one core, "shared core of the joint
+// q'-batch kernels" below: Sigma = [[v0, c^T], [c, cov_pp]], its Cholesky factor with the jitter ladder, and the draw
+// y = m + L z, once for a factor in strided memory (LDS or the global workspace) and once for a factor in registers.  A kernel
+// adds its storage and its utility; the host side shares the upload, the 60 KB rule and the Q = 2 ... 14 dispatch.
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "bbh_common.h"
 #include "bbh_acqmath.h"  // TAU_RELU, bbh_fatplus_core, bbh_safe_sd
 
 #define TAU_MAX 1e-2
 #define LOG_TAU_RELU -13.815510557964274  // log(1e-6)
-#ifndef BBH_PENDING_LSE
-#define BBH_PENDING_LSE 0
-#endif
 typedef float bbh_f2 __attribute__((ext_vector_type(2)));
 #ifndef BBH_PENDING_PK
 #define BBH_PENDING_PK 1  // (with BBH_PENDING_FAST) the u_r^2 terms of the fat maximum in packed single precision, two points at a time
@@ -61,33 +65,24 @@ __global__ __launch_bounds__(256) void bbh_qlogei_q1_kernel(const double* __rest
   scores[i] = log(TAU_RELU) + log(sum) - log((double)S);
 }
 
-// q' = 1 + p with pending points.  Thread-private packed lower-triangular Cholesky in LDS
-// (element e of thread t at s_L[e * 64 + t]); exact psd_safe_cholesky semantics (jitter retries).
+// ---- shared core of the joint q'-batch kernels ----------------------------------------------------------------------------
+// q' = 1 + p points: the candidate, then the p pending points.  Per candidate: Sigma = [[v0, c^T], [c, cov_pp]] (v0 = var[i],
+// c = cross[i p ...]), its Cholesky factor with exact psd_safe_cholesky semantics - diagonal jitter 0, 1e-8, 1e-7, 1e-6, a pivot
+// !(s > 0) ends an attempt, no factor after the fourth (gpytorch raises NotPSDError; the kernels score NaN) - and per base sample
+// the draw y_r = m_r + sum_c L_rc z_c.  The factor is thread-private, packed lower-triangular (element (r, c) at tri(r, c)), and
+// these three pieces are written once per storage class:
+//   strided memory, run-time q'  element e at L[e * stride]: stride 64 in LDS (bbh_qlogei_pending_kernel, bbh_mc_pending_kernel),
+//                                stride N in a global workspace (bbh_qlogei_pending_big_kernel); a failed pivot breaks out
+//   registers, template <int Q>  every index a compile-time constant (bbh_qlogei_pending_q_kernel, bbh_mc_pending_q_kernel);
+//                                a failed pivot lets the attempt run on and discards it
+// Both factor row by row with the k loop subtracting in ascending order, and draw by fma in ascending c from the mean.
 #define QMAX 16
 #define QTRI (QMAX * (QMAX + 1) / 2)
 __device__ __forceinline__ int tri(int i, int j) { return i * (i + 1) / 2 + j; }
 
-__global__ __launch_bounds__(64) void bbh_qlogei_pending_kernel(
-    const double* __restrict__ mean, const double* __restrict__ var, const double* __restrict__ cross, int64_t N, int p,
-    const double* __restrict__ mean_p, const double* __restrict__ cov_pp, const double* __restrict__ z, int S,
-    double best_f, double sign, const uint8_t* __restrict__ alive, double* __restrict__ scores) {
-  __shared__ double s_L[QTRI * 64];
-  __shared__ double s_mp[QMAX];
-  __shared__ double s_cpp[QMAX * QMAX];
-  const int t = threadIdx.x;
+template <typename ST>  // ST: type of the stride (int 64, int64_t N)
+__device__ __forceinline__ bool bbh_joint_factor(double* L, ST stride, int p, double v0, const double* cross_i, const double* cov_pp) {
   const int q = p + 1;
-  for (int e = t; e < p; e += 64) s_mp[e] = mean_p[e];
-  for (int e = t; e < p * p; e += 64) s_cpp[e] = cov_pp[e];
-  __syncthreads();
-  const int64_t i = (int64_t)blockIdx.x * 64 + t;
-  if (i >= N) return;
-  if (alive && !alive[i]) {
-    scores[i] = -INFINITY;
-    return;
-  }
-  double* L = s_L + t;  // L[tri(i,j) * 64]
-  const double v0 = var[i];
-  // Cholesky of Sigma = [[v0, c^T], [c, cov_pp]] with diagonal jitter retries
   double jitter = 0.0;
   bool ok = false;
   for (int attempt = 0; attempt < 4 && !ok; attempt++) {
@@ -98,51 +93,59 @@ __global__ __launch_bounds__(64) void bbh_qlogei_pending_kernel(
         if (r == 0)
           s = v0;
         else if (c == 0)
-          s = cross[i * p + (r - 1)];
+          s = cross_i[r - 1];
         else
-          s = s_cpp[(r - 1) * p + (c - 1)];
+          s = cov_pp[(r - 1) * p + (c - 1)];
         if (r == c) s += jitter;
-        for (int k = 0; k < c; k++) s -= L[tri(r, k) * 64] * L[tri(c, k) * 64];
+        for (int k = 0; k < c; k++) s -= L[tri(r, k) * stride] * L[tri(c, k) * stride];
         if (r == c) {
           if (!(s > 0.0)) {
             ok = false;
             break;
           }
-          L[tri(r, r) * 64] = sqrt(s);
+          L[tri(r, r) * stride] = sqrt(s);
         } else {
-          L[tri(r, c) * 64] = s / L[tri(c, c) * 64];
+          L[tri(r, c) * stride] = s / L[tri(c, c) * stride];
         }
       }
     }
     if (!ok) jitter = 1e-8 * pow(10.0, (double)attempt);
   }
-  if (!ok) {
-    scores[i] = NAN;  // not PSD even with jitter 1e-6 (gpytorch raises NotPSDError)
-    return;
-  }
-  const double m0 = mean[i];
+  return ok;
+}
+
+template <typename ST>
+__device__ __forceinline__ double bbh_joint_draw(const double* L, ST stride, int r, double m, const double* zs) {
+  double y = m;
+  for (int c = 0; c <= r; c++) y = fma(L[tri(r, c) * stride], zs[c], y);
+  return y;
+}
+
+// qLogEI of one candidate from its strided factor: per sample li_r = log_fatplus(sign y_r - best_f), the fat maximum over the q'
+// points, a streaming log-sum-exp over the samples.  li: q' doubles of this thread, element r at li[r * li_stride].
+template <typename ST>
+__device__ __forceinline__ double bbh_qlogei_joint_lse(const double* L, ST stride, int q, double m0, const double* mean_p,
+                                                       const double* z, int S, double best_f, double sign, double* li,
+                                                       int li_stride) {
   const double inv_tau = 1.0 / TAU_RELU;
-  double sum = 0.0;  // sum_s exp(fatmax_s - ref), streaming log-sum-exp
+  double sum = 0.0;  // sum_s exp(fatmax_s - ref)
   double ref = -INFINITY;
   for (int s = 0; s < S; s++) {
     const double* zs = z + (int64_t)s * q;
-    // li_j = log_fatplus(sign * y_j - best_f), y = m + L z
-    double li[QMAX];
     double mx = -INFINITY;
 #pragma unroll 1
     for (int r = 0; r < q; r++) {
-      double y = (r == 0) ? m0 : s_mp[r - 1];
-      for (int c = 0; c <= r; c++) y = fma(L[tri(r, c) * 64], zs[c], y);
+      const double y = bbh_joint_draw(L, stride, r, (r == 0) ? m0 : mean_p[r - 1], zs);
       const double tt = (sign * y - best_f) * inv_tau;
       const double v = log(TAU_RELU) + log(bbh_fatplus_core(tt));
-      li[r] = v;
+      li[r * li_stride] = v;
       mx = fmax(mx, v);
     }
     // fatmax over the q' points: mx + tau log sum_j (2 / (2 + (mx - li_j)/tau))^2
     double acc = 0.0;
 #pragma unroll 1
     for (int r = 0; r < q; r++) {
-      const double u = 2.0 / (2.0 + (mx - li[r]) / TAU_MAX);
+      const double u = 2.0 / (2.0 + (mx - li[r * li_stride]) / TAU_MAX);
       acc = fma(u, u, acc);
     }
     const double fm = mx + TAU_MAX * log(acc);
@@ -153,7 +156,87 @@ __global__ __launch_bounds__(64) void bbh_qlogei_pending_kernel(
       sum += exp(fm - ref);
     }
   }
-  scores[i] = ref + log(sum) - log((double)S);
+  return ref + log(sum) - log((double)S);
+}
+
+template <int Q>
+__device__ __forceinline__ void bbh_joint_load_q(double (&A)[Q * (Q + 1) / 2], double v0, const double* cross_i, const double* s_cpp) {
+  constexpr int P = Q - 1;
+  A[0] = v0;  // lower triangle of Sigma
+#pragma unroll
+  for (int r = 1; r < Q; r++) {
+    A[r * (r + 1) / 2] = cross_i[r - 1];
+#pragma unroll
+    for (int c = 1; c <= r; c++) A[r * (r + 1) / 2 + c] = s_cpp[(r - 1) * P + (c - 1)];
+  }
+}
+
+template <int Q>
+__device__ __forceinline__ bool bbh_joint_factor_q(const double (&A)[Q * (Q + 1) / 2], double (&L)[Q * (Q + 1) / 2]) {
+  double jitter = 0.0;
+  bool ok = false;
+  for (int attempt = 0; attempt < 4 && !ok; attempt++) {
+    ok = true;
+#pragma unroll
+    for (int r = 0; r < Q; r++) {
+#pragma unroll
+      for (int c = 0; c <= r; c++) {
+        double sacc = A[r * (r + 1) / 2 + c];
+        if (r == c) sacc += jitter;
+#pragma unroll
+        for (int k = 0; k < c; k++) sacc -= L[r * (r + 1) / 2 + k] * L[c * (c + 1) / 2 + k];
+        if (r == c) {
+          if (!(sacc > 0.0)) ok = false;  // the rest of this attempt is discarded (values may be NaN)
+          L[r * (r + 1) / 2 + r] = sqrt(sacc);
+        } else {
+          L[r * (r + 1) / 2 + c] = sacc / L[c * (c + 1) / 2 + c];
+        }
+      }
+    }
+    if (!ok) jitter = 1e-8 * pow(10.0, (double)attempt);
+  }
+  return ok;
+}
+
+template <int Q>
+__device__ __forceinline__ void bbh_joint_draw_q(const double (&L)[Q * (Q + 1) / 2], const double (&m)[Q], const double* zs,
+                                                 double (&y)[Q]) {
+  double zr[Q];
+#pragma unroll
+  for (int c = 0; c < Q; c++) zr[c] = zs[c];
+#pragma unroll
+  for (int r = 0; r < Q; r++) {
+    y[r] = m[r];
+#pragma unroll
+    for (int c = 0; c <= r; c++) y[r] = fma(L[r * (r + 1) / 2 + c], zr[c], y[r]);
+  }
+}
+
+// q' <= 16: the factor in LDS (element e of thread t at s_L[e * 64 + t]), log-domain streaming form.
+__global__ __launch_bounds__(64) void bbh_qlogei_pending_kernel(
+    const double* __restrict__ mean, const double* __restrict__ var, const double* __restrict__ cross, int64_t N, int p,
+    const double* __restrict__ mean_p, const double* __restrict__ cov_pp, const double* __restrict__ z, int S,
+    double best_f, double sign, const uint8_t* __restrict__ alive, double* __restrict__ scores) {
+  __shared__ double s_L[QTRI * 64];
+  __shared__ double s_mp[QMAX];
+  __shared__ double s_cpp[QMAX * QMAX];
+  const int t = threadIdx.x;
+  for (int e = t; e < p; e += 64) s_mp[e] = mean_p[e];
+  for (int e = t; e < p * p; e += 64) s_cpp[e] = cov_pp[e];
+  __syncthreads();
+  const int64_t i = (int64_t)blockIdx.x * 64 + t;
+  if (i >= N) return;
+  if (alive && !alive[i]) {
+    scores[i] = -INFINITY;
+    return;
+  }
+  double* L = s_L + t;
+  double li[QMAX];
+  if (!bbh_joint_factor(L, 64, p, var[i], cross + i * p, s_cpp)) {
+    scores[i] = NAN;  // not PSD even with jitter 1e-6
+    return;
+  }
+  scores[i] = bbh_qlogei_joint_lse(L, 64, p + 1, mean[i], s_mp, z, S, best_f, sign, li, 1);
 }
 
 // log(x) for positive, finite, normal x (the fat-softplus values and sums of squares below): exponent and
@@ -189,8 +272,9 @@ __device__ __forceinline__ double bbh_fast_log_pos(double x) {
   return (x < INFINITY) ? r2 : x;  // log(inf) = inf (NaN propagates)
 }
 
-// Register-resident form of the kernel above for q' = Q <= 14 (208 VGPRs at Q = 8, 2 waves per SIMD from Q = 9,
-// 1 from Q = 10, no spills up to Q = 14; Q = 15, 16 spill and run no faster than the LDS form): the packed Cholesky
+// Register-resident form of bbh_qlogei_pending_kernel for q' = Q <= 14 (208 VGPRs at Q = 8, 2 waves per SIMD from Q = 9,
+// 1 from Q = 10; no spills up to Q = 13, Q = 14 reports 4 spilled VGPRs and no scratch memory: .vgpr_spill_count 4,
+// .private_segment_fixed_size 0; Q = 15, 16 spill further and run no faster than the LDS form): the packed Cholesky
 // factor (Q (Q + 1) / 2 doubles) and the per-sample values live in registers (every index is a
 // compile-time constant), the base samples z [S, Q] in LDS (broadcast reads).  The LDS form needs 69 KB
 // per 64 threads - one wave per two SIMDs - and took 30 ms per greedy step on 1e6 candidates, six times the
@@ -228,38 +312,9 @@ __global__ __launch_bounds__(256) void bbh_qlogei_pending_q_kernel(
     scores[i] = partial ? 0.0 : -INFINITY;
     return;
   }
-  double L[Q * (Q + 1) / 2];
-  double A[Q * (Q + 1) / 2];  // lower triangle of Sigma = [[v0, c^T], [c, cov_pp]]
-  A[0] = var[i];
-#pragma unroll
-  for (int r = 1; r < Q; r++) {
-    A[r * (r + 1) / 2] = cross[i * P + (r - 1)];
-#pragma unroll
-    for (int c = 1; c <= r; c++) A[r * (r + 1) / 2 + c] = s_cpp[(r - 1) * P + (c - 1)];
-  }
-  double jitter = 0.0;
-  bool ok = false;
-  for (int attempt = 0; attempt < 4 && !ok; attempt++) {
-    ok = true;
-#pragma unroll
-    for (int r = 0; r < Q; r++) {
-#pragma unroll
-      for (int c = 0; c <= r; c++) {
-        double sacc = A[r * (r + 1) / 2 + c];
-        if (r == c) sacc += jitter;
-#pragma unroll
-        for (int k = 0; k < c; k++) sacc -= L[r * (r + 1) / 2 + k] * L[c * (c + 1) / 2 + k];
-        if (r == c) {
-          if (!(sacc > 0.0)) ok = false;  // the rest of this attempt is discarded (values may be NaN)
-          L[r * (r + 1) / 2 + r] = sqrt(sacc);
-        } else {
-          L[r * (r + 1) / 2 + c] = sacc / L[c * (c + 1) / 2 + c];
-        }
-      }
-    }
-    if (!ok) jitter = 1e-8 * pow(10.0, (double)attempt);
-  }
-  if (!ok) {
+  double L[Q * (Q + 1) / 2], A[Q * (Q + 1) / 2];
+  bbh_joint_load_q<Q>(A, var[i], cross + i * P, s_cpp);
+  if (!bbh_joint_factor_q<Q>(A, L)) {
     scores[i] = NAN;  // not PSD even with jitter 1e-6 (gpytorch raises NotPSDError)
     return;
   }
@@ -271,33 +326,24 @@ __global__ __launch_bounds__(256) void bbh_qlogei_pending_q_kernel(
   // exp(fatmax_s) = exp(mx_s) acc_s^tau_max with exp(mx_s) = tau_relu max_r fatplus_core(t_sr): the per-sample
   // exponential of the streaming log-sum-exp and the logarithm of the largest term are not needed.  The terms
   // tau_relu^-1 exp(fatmax_s) lie in [1e-41, 1e7) for every reachable t, so the plain sum neither overflows nor
-  // loses its smallest terms to underflow (BBH_PENDING_LSE=1 at compile time restores the streaming form).
+  // loses its smallest terms to underflow (the streaming form is bbh_qlogei_pending_kernel: BBH_PENDING_LDS=1).
   double sum = 0.0;
-#if BBH_PENDING_LSE
-  double ref = -INFINITY;
-#endif
-#if BBH_PENDING_FAST && !BBH_PENDING_LSE
-  // exp(fatmax_s) / tau_relu = fmx acc^tau_max with fmx = max_r fatplus(t_sr) and acc = sum_r u_r^2, u_r = 2 tau / (2 tau + D_r),
-  // D_r = log(fmx / fatplus(t_sr)) >= 0.  fmx enters linearly and is kept to full precision, but acc enters through the power
-  // tau_max = 0.01: an absolute error of 1e-7 in u_r^2 changes the sample's term by 1e-9 relative.  So D_r never needs a
-  // double-precision logarithm:  rho = fatplus_r / fmx, x = 1 - rho;  x < 0.15: D = -log1p(-x) = x + x^2/2 + ... + x^7/7
-  // (truncation 3e-8 at the edge, where u = 0.11 and du^2/dD = 100 u^3 = 0.13);  otherwise D = -ln 2 log2f(rho) in single
-  // precision (error ~1e-7; rho below the float range gives D = inf, u = 0: u^2 < 6e-8 there anyway).  The reciprocal is the
-  // bare v_rcp_f64 seed (2^-26), log(acc) for acc in [1, Q] single precision as well.  Per sample and point ~33 instead of
-  // ~55 VALU instructions, per sample 13 instead of 34 (BBH_PENDING_FAST=0 at compile time restores the former sequence).
   for (int s = 0; s < S; s++) {
-    const double* zs = s_zq + (int64_t)s * Q;
-    double zr[Q], fp[Q];
-#pragma unroll
-    for (int c = 0; c < Q; c++) zr[c] = zs[c];
+    double y[Q], fp[Q];
+    bbh_joint_draw_q<Q>(L, m, s_zq + (int64_t)s * Q, y);
     double fmx = 0.0;
+#if BBH_PENDING_FAST
+    // exp(fatmax_s) / tau_relu = fmx acc^tau_max with fmx = max_r fatplus(t_sr) and acc = sum_r u_r^2, u_r = 2 tau / (2 tau + D_r),
+    // D_r = log(fmx / fatplus(t_sr)) >= 0.  fmx enters linearly and is kept to full precision, but acc enters through the power
+    // tau_max = 0.01: an absolute error of 1e-7 in u_r^2 changes the sample's term by 1e-9 relative.  So D_r never needs a
+    // double-precision logarithm:  rho = fatplus_r / fmx, x = 1 - rho;  x < 0.15: D = -log1p(-x) = x + x^2/2 + ... + x^7/7
+    // (truncation 3e-8 at the edge, where u = 0.11 and du^2/dD = 100 u^3 = 0.13);  otherwise D = -ln 2 log2f(rho) in single
+    // precision (error ~1e-7; rho below the float range gives D = inf, u = 0: u^2 < 6e-8 there anyway).  The reciprocal is the
+    // bare v_rcp_f64 seed (2^-26), log(acc) for acc in [1, Q] single precision as well.  Per sample and point ~33 instead of
+    // ~55 VALU instructions, per sample 13 instead of 34 (BBH_PENDING_FAST=0 at compile time restores the former sequence).
 #pragma unroll
     for (int r = 0; r < Q; r++) {
-      double y = m[r];
-#pragma unroll
-      for (int c = 0; c <= r; c++) y = fma(L[r * (r + 1) / 2 + c], zr[c], y);
-      const double tt = (sign * y - best_f) * inv_tau;
-      fp[r] = bbh_fatplus_core<1>(tt);
+      fp[r] = bbh_fatplus_core<1>((sign * y[r] - best_f) * inv_tau);
       fmx = fmax(fmx, fp[r]);
     }
 #if BBH_PENDING_PK
@@ -334,12 +380,6 @@ __global__ __launch_bounds__(256) void bbh_qlogei_pending_q_kernel(
     }
     const float accf = accp.x + accp.y;
     const double w = (TAU_MAX * 0.6931471805599453) * (double)__log2f(accf);
-    double e = fma(w, 1.0 / 120.0, 1.0 / 24.0);
-    e = fma(e, w, 1.0 / 6.0);
-    e = fma(e, w, 0.5);
-    e = fma(e, w, 1.0);
-    e = fma(e, w, 1.0);
-    sum = fma(fmx, e, sum);
 #else
     double inv = __builtin_amdgcn_rcp(fmx);
     inv = fma(fma(-fmx, inv, 1.0), inv, inv);
@@ -360,30 +400,19 @@ __global__ __launch_bounds__(256) void bbh_qlogei_pending_q_kernel(
       const double u = (2.0 * TAU_MAX) * __builtin_amdgcn_rcp(2.0 * TAU_MAX + dd);  // dd = inf -> 0
       acc = fma(u, u, acc);
     }
-    // acc in [1, Q]: acc^0.01 = exp(w), w = 0.01 ln acc in [0, 0.028): Taylor to the 5th power (7e-13 at w = 0.028)
     const double w = (TAU_MAX * 0.6931471805599453) * (double)__log2f((float)acc);
+#endif
+    // acc in [1, Q]: acc^0.01 = exp(w), w = 0.01 ln acc in [0, 0.028): Taylor to the 5th power (7e-13 at w = 0.028)
     double e = fma(w, 1.0 / 120.0, 1.0 / 24.0);
     e = fma(e, w, 1.0 / 6.0);
     e = fma(e, w, 0.5);
     e = fma(e, w, 1.0);
     e = fma(e, w, 1.0);
-    sum = fma(fmx, e, sum);
-#endif
-  }
 #else
-  for (int s = 0; s < S; s++) {
-    const double* zs = s_zq + (int64_t)s * Q;
-    double zr[Q], li[Q], fp[Q];
-#pragma unroll
-    for (int c = 0; c < Q; c++) zr[c] = zs[c];
-    double fmx = 0.0;
+    double li[Q];
 #pragma unroll
     for (int r = 0; r < Q; r++) {
-      double y = m[r];
-#pragma unroll
-      for (int c = 0; c <= r; c++) y = fma(L[r * (r + 1) / 2 + c], zr[c], y);
-      const double tt = (sign * y - best_f) * inv_tau;
-      fp[r] = bbh_fatplus_core(tt);
+      fp[r] = bbh_fatplus_core((sign * y[r] - best_f) * inv_tau);
       fmx = fmax(fmx, fp[r]);
     }
     double mx = -INFINITY;
@@ -398,15 +427,6 @@ __global__ __launch_bounds__(256) void bbh_qlogei_pending_q_kernel(
       const double u = (2.0 * TAU_MAX) * bbh_fast_recip(2.0 * TAU_MAX + (mx - li[r]));
       acc = fma(u, u, acc);
     }
-#if BBH_PENDING_LSE
-    const double fm = fma(TAU_MAX, bbh_fast_log_pos(acc), mx + LOG_TAU_RELU);
-    if (fm > ref) {
-      sum = sum * exp(ref - fm) + 1.0;
-      ref = fm;
-    } else {
-      sum += exp(fm - ref);
-    }
-#else
     // acc in [1, Q]: acc^0.01 = exp(0.01 log acc), argument in [0, 0.021) - Taylor to the 6th power (1e-17)
     const double w = TAU_MAX * bbh_fast_log_pos(acc);
     double e = fma(w, 1.0 / 720.0, 1.0 / 120.0);
@@ -415,15 +435,10 @@ __global__ __launch_bounds__(256) void bbh_qlogei_pending_q_kernel(
     e = fma(e, w, 0.5);
     e = fma(e, w, 1.0);
     e = fma(e, w, 1.0);
+#endif
     sum = fma(fmx, e, sum);
-#endif
   }
-#endif
-#if BBH_PENDING_LSE
-  scores[i] = ref + log(sum) - log((double)S);
-#else
   scores[i] = partial ? sum : LOG_TAU_RELU + log(sum) - log((double)S_total);
-#endif
 }
 
 __global__ __launch_bounds__(256) void bbh_pending_finish_kernel(const double* __restrict__ partial, int slices, int64_t N, int S,
@@ -605,6 +620,48 @@ int bbh_qlogei_q1_rounds(bbh_handle* h, const double* mean_dev, const double* va
   return 0;
 }
 
+// One upload per joint launch: [z [S, q'] | zbar [q'] (column means of z: the MC family only) | mean_p [p] | cov_pp [p, p]]
+struct bbh_joint_dev {
+  const double *z, *zbar, *mean_p, *cov_pp;
+  size_t bytes;  // of the whole upload
+};
+static int bbh_upload_joint(bbh_handle* h, const double* z_host, int64_t S, int64_t p, const double* mp_host, const double* cpp_host,
+                            bool with_zbar, bbh_joint_dev* d) {
+  const int64_t q = p + 1, nzb = with_zbar ? q : 0;
+  std::vector<double> buf((size_t)S * q + nzb + p + (size_t)p * p, 0.0);
+  memcpy(buf.data(), z_host, sizeof(double) * S * q);
+  double* zb = buf.data() + S * q;
+  if (with_zbar) {
+    for (int64_t s = 0; s < S; s++)
+      for (int c = 0; c < q; c++) zb[c] += z_host[s * q + c];
+    for (int c = 0; c < q; c++) zb[c] /= (double)S;
+  }
+  memcpy(zb + nzb, mp_host, sizeof(double) * p);
+  memcpy(zb + nzb + p, cpp_host, sizeof(double) * p * p);
+  const int rc = bbh_upload_z(h, buf.data(), buf.size());
+  if (rc) return rc;
+  d->z = h->d_z;
+  d->zbar = with_zbar ? d->z + S * q : nullptr;
+  d->mean_p = d->z + S * q + nzb;
+  d->cov_pp = d->mean_p + p;
+  d->bytes = sizeof(double) * buf.size();
+  return 0;
+}
+
+// The register forms hold the base samples and the pending statistics in LDS: an upload of at most 60 KB
+static bool bbh_fits_register_form(size_t upload_bytes) { return upload_bytes <= 60 * 1024; }
+
+// f(std::integral_constant<int, Q>) for Q == q in 2 ... 14 (the register forms' instantiations); false for any other q
+template <int Q = 2, class F>
+static bool bbh_dispatch_q(int q, F&& f) {
+  if constexpr (Q <= 14) {
+    if (q != Q) return bbh_dispatch_q<Q + 1>(q, f);
+    f(std::integral_constant<int, Q>());
+    return true;
+  }
+  return false;
+}
+
 // p <= 15 pending points with the pending statistics given explicitly (the handle's own, or a caller's - see
 // bbh_qlogei_pending_big)
 static int bbh_qlogei_pending_impl(bbh_handle* h, const double* mean_dev, const double* var_dev, const double* cross_dev, int64_t N,
@@ -633,22 +690,14 @@ static int bbh_qlogei_pending_impl(bbh_handle* h, const double* mean_dev, const 
   }
   if (N == 0) return 0;
   BBH_HIP_TRY(h, hipSetDevice(h->device));
-  // device buffer: z [S, 1+p] followed by the pending posterior mean_p [p], cov_pp [p,p]
-  int rc;
-  std::vector<double> buf((size_t)S * (p + 1) + p + (size_t)p * p);
-  memcpy(buf.data(), z_host, sizeof(double) * S * (p + 1));
-  memcpy(buf.data() + S * (p + 1), mp_host, sizeof(double) * p);
-  memcpy(buf.data() + S * (p + 1) + p, cpp_host, sizeof(double) * p * p);
-  rc = bbh_upload_z(h, buf.data(), buf.size());
+  bbh_joint_dev d;
+  int rc = bbh_upload_joint(h, z_host, S, p, mp_host, cpp_host, false, &d);
   if (rc) return rc;
-  const double* dz = h->d_z;
-  const double* dmp = dz + S * (p + 1);
-  const double* dcpp = dmp + p;
-  const bool fits = sizeof(double) * ((size_t)S * (p + 1) + p + (size_t)p * p) <= 60 * 1024;  // z in LDS
+  const bool reg_form = bbh_fits_register_form(d.bytes) && !h->sw.pending_lds_form;
   // sample slices for small candidate sets (~16 waves per SIMD; linear-domain form; each slice at least 32 samples)
   int slices = 1;
-#if BBH_PENDING_FAST && !BBH_PENDING_LSE
-  if (fits && !h->sw.pending_lds_form && p + 1 <= 14) {
+#if BBH_PENDING_FAST
+  if (reg_form && p + 1 <= 14) {
     int64_t want = ((int64_t)16 * 4 * h->num_cu * 64) / (h->slice_rows > 0 ? h->slice_rows : N);
     if (h->sw.pending_slices != INT_MIN) want = h->sw.pending_slices;
     if (want > S / 32) want = S / 32;
@@ -660,30 +709,12 @@ static int bbh_qlogei_pending_impl(bbh_handle* h, const double* mean_dev, const 
   }
 #endif
   bbh_timed_scope timed(h, BBH_TIMED_PENDING);
-#define BBH_PENDING_Q(QV)                                                                                        \
-  case QV:                                                                                                       \
-    bbh_launch_pending_q<QV>(h->stream, mean_dev, var_dev, cross_dev, N, dmp, dcpp, dz, (int)S, best_f, sign,    \
-                             alive_dev, scores_dev, slices, h->d_ws);                                            \
-    break;
-  switch (fits && !h->sw.pending_lds_form ? p + 1 : 0) {
-    BBH_PENDING_Q(2)
-    BBH_PENDING_Q(3)
-    BBH_PENDING_Q(4)
-    BBH_PENDING_Q(5)
-    BBH_PENDING_Q(6)
-    BBH_PENDING_Q(7)
-    BBH_PENDING_Q(8)
-    BBH_PENDING_Q(9)
-    BBH_PENDING_Q(10)
-    BBH_PENDING_Q(11)
-    BBH_PENDING_Q(12)
-    BBH_PENDING_Q(13)
-    BBH_PENDING_Q(14)
-    default:
-      hipLaunchKernelGGL(bbh_qlogei_pending_kernel, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, h->stream, mean_dev,
-                         var_dev, cross_dev, N, p, dmp, dcpp, dz, (int)S, best_f, sign, alive_dev, scores_dev);
-  }
-#undef BBH_PENDING_Q
+  if (!(reg_form && bbh_dispatch_q(p + 1, [&](auto Q) {
+          bbh_launch_pending_q<decltype(Q)::value>(h->stream, mean_dev, var_dev, cross_dev, N, d.mean_p, d.cov_pp, d.z, (int)S, best_f,
+                                                   sign, alive_dev, scores_dev, slices, h->d_ws);
+        })))
+    hipLaunchKernelGGL(bbh_qlogei_pending_kernel, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, h->stream, mean_dev, var_dev,
+                       cross_dev, N, p, d.mean_p, d.cov_pp, d.z, (int)S, best_f, sign, alive_dev, scores_dev);
   BBH_HIP_TRY(h, hipGetLastError());
   return 0;
 }
@@ -692,8 +723,8 @@ static int bbh_qlogei_pending_impl(bbh_handle* h, const double* mean_dev, const 
 // The reference has no cap on batch_size + pending experiments (botorch/discrete.py:120-126); the register form above holds
 // q' <= 14, the LDS form q' <= 16.  For larger q' the thread-private Cholesky factor (q' (q' + 1) / 2 doubles: 4.2 KB at q' = 32)
 // lives in a global workspace, element e of candidate i at Lws[e N + i] (coalesced across the wave), the per-sample
-// log-fat-softplus values in LDS ([q'][64]); mean_p / cov_pp / z are read from global memory at wave-uniform addresses.  Same
-// arithmetic and operation order as bbh_qlogei_pending_kernel (log-domain streaming form, psd_safe_cholesky's jitter retries).
+// log-fat-softplus values in LDS ([q'][64]); mean_p / cov_pp / z are read from global memory at wave-uniform addresses.  The
+// same routines as bbh_qlogei_pending_kernel (log-domain streaming form, psd_safe_cholesky's jitter retries) over stride N.
 // Memory-bound on the factor (q'^2 / 2 loads per sample): ~0.1 s per 1e5 candidates at q' = 32 - a correctness path for the
 // rare large batch, not a tuned one.
 #define QBIG_MAX 64
@@ -704,75 +735,18 @@ __global__ __launch_bounds__(64) void bbh_qlogei_pending_big_kernel(
     double best_f, double sign, const uint8_t* __restrict__ alive, double* __restrict__ scores, double* __restrict__ Lws) {
   extern __shared__ double s_li[];  // [q][64]
   const int t = threadIdx.x;
-  const int q = p + 1;
   const int64_t i = (int64_t)blockIdx.x * 64 + t;
   if (i >= N) return;
   if (alive && !alive[i]) {
     scores[i] = -INFINITY;
     return;
   }
-  double* L = Lws + i;  // L[tri(r, c) * N]
-  const double v0 = var[i];
-  double jitter = 0.0;
-  bool ok = false;
-  for (int attempt = 0; attempt < 4 && !ok; attempt++) {
-    ok = true;
-    for (int r = 0; r < q && ok; r++) {
-      for (int c = 0; c <= r; c++) {
-        double sacc;
-        if (r == 0)
-          sacc = v0;
-        else if (c == 0)
-          sacc = cross[i * p + (r - 1)];
-        else
-          sacc = cov_pp[(r - 1) * p + (c - 1)];
-        if (r == c) sacc += jitter;
-        for (int k = 0; k < c; k++) sacc -= L[(int64_t)tri(r, k) * N] * L[(int64_t)tri(c, k) * N];
-        if (r == c) {
-          if (!(sacc > 0.0)) {
-            ok = false;
-            break;
-          }
-          L[(int64_t)tri(r, r) * N] = sqrt(sacc);
-        } else {
-          L[(int64_t)tri(r, c) * N] = sacc / L[(int64_t)tri(c, c) * N];
-        }
-      }
-    }
-    if (!ok) jitter = 1e-8 * pow(10.0, (double)attempt);
-  }
-  if (!ok) {
+  double* L = Lws + i;
+  if (!bbh_joint_factor(L, N, p, var[i], cross + i * p, cov_pp)) {
     scores[i] = NAN;
     return;
   }
-  const double m0 = mean[i];
-  const double inv_tau = 1.0 / TAU_RELU;
-  double sum = 0.0, ref = -INFINITY;
-  for (int s = 0; s < S; s++) {
-    const double* zs = z + (int64_t)s * q;
-    double mx = -INFINITY;
-    for (int r = 0; r < q; r++) {
-      double y = (r == 0) ? m0 : mean_p[r - 1];
-      for (int c = 0; c <= r; c++) y = fma(L[(int64_t)tri(r, c) * N], zs[c], y);
-      const double tt = (sign * y - best_f) * inv_tau;
-      const double v = log(TAU_RELU) + log(bbh_fatplus_core(tt));
-      s_li[r * 64 + t] = v;
-      mx = fmax(mx, v);
-    }
-    double acc = 0.0;
-    for (int r = 0; r < q; r++) {
-      const double u = 2.0 / (2.0 + (mx - s_li[r * 64 + t]) / TAU_MAX);
-      acc = fma(u, u, acc);
-    }
-    const double fm = mx + TAU_MAX * log(acc);
-    if (fm > ref) {
-      sum = sum * exp(ref - fm) + 1.0;
-      ref = fm;
-    } else {
-      sum += exp(fm - ref);
-    }
-  }
-  scores[i] = ref + log(sum) - log((double)S);
+  scores[i] = bbh_qlogei_joint_lse(L, N, p + 1, mean[i], mean_p, z, S, best_f, sign, s_li + t, 64);
 }
 
 extern "C" int bbh_qlogei_pending_big(bbh_handle* h, const double* mean_dev, const double* var_dev, const double* cross_dev,
@@ -791,11 +765,8 @@ extern "C" int bbh_qlogei_pending_big(bbh_handle* h, const double* mean_dev, con
                                    alive_dev, scores_dev);
   BBH_HIP_TRY(h, hipSetDevice(h->device));
   const int64_t q = p + 1;
-  std::vector<double> buf((size_t)S * q + p + (size_t)p * p);
-  memcpy(buf.data(), z_host, sizeof(double) * S * q);
-  memcpy(buf.data() + S * q, mean_p_host, sizeof(double) * p);
-  memcpy(buf.data() + S * q + p, cov_pp_host, sizeof(double) * p * p);
-  int rc = bbh_upload_z(h, buf.data(), buf.size());
+  bbh_joint_dev d;
+  int rc = bbh_upload_joint(h, z_host, S, p, mean_p_host, cov_pp_host, false, &d);
   if (rc) return rc;
   // The per-candidate factor workspace is q'(q' + 1) / 2 doubles: 16 GB for 1e6 candidates at q' = 64.  The candidates are walked in
   // chunks whose workspace stays below QBIG_WS_BYTES (the handle's grow-only workspace outlives the call, also in the handle pool);
@@ -807,12 +778,11 @@ extern "C" int bbh_qlogei_pending_big(bbh_handle* h, const double* mean_dev, con
   if (chunk > N) chunk = N;
   rc = bbh_ensure_ws(h, sizeof(double) * (size_t)tri_q * (size_t)chunk);
   if (rc) return rc;
-  const double* dz = h->d_z;
   bbh_timed_scope timed(h, BBH_TIMED_PENDING);
   for (int64_t c0 = 0; c0 < N; c0 += chunk) {
     const int64_t nc = std::min(chunk, N - c0);
     hipLaunchKernelGGL(bbh_qlogei_pending_big_kernel, dim3((unsigned)((nc + 63) / 64)), dim3(64), sizeof(double) * q * 64, h->stream,
-                       mean_dev + c0, var_dev + c0, cross_dev + c0 * p, nc, (int)p, dz + S * q, dz + S * q + p, dz, (int)S, best_f, sign,
+                       mean_dev + c0, var_dev + c0, cross_dev + c0 * p, nc, (int)p, d.mean_p, d.cov_pp, d.z, (int)S, best_f, sign,
                        alive_dev ? alive_dev + c0 : nullptr, scores_dev + c0, h->d_ws);
   }
   BBH_HIP_TRY(h, hipGetLastError());
@@ -1539,49 +1509,21 @@ __global__ __launch_bounds__(64) void bbh_mc_pending_kernel(int kind, const doub
     return;
   }
   double* L = s_L + t;
-  const double v0 = var[i];
-  double jitter = 0.0;
-  bool ok = false;
-  for (int attempt = 0; attempt < 4 && !ok; attempt++) {
-    ok = true;
-    for (int r = 0; r < q && ok; r++) {
-      for (int c = 0; c <= r; c++) {
-        double s = (r == 0) ? v0 : (c == 0 ? cross[i * p + (r - 1)] : s_cpp[(r - 1) * p + (c - 1)]);
-        if (r == c) s += jitter;
-        for (int k = 0; k < c; k++) s -= L[tri(r, k) * 64] * L[tri(c, k) * 64];
-        if (r == c) {
-          if (!(s > 0.0)) {
-            ok = false;
-            break;
-          }
-          L[tri(r, r) * 64] = sqrt(s);
-        } else {
-          L[tri(r, c) * 64] = s / L[tri(c, c) * 64];
-        }
-      }
-    }
-    if (!ok) jitter = 1e-8 * pow(10.0, (double)attempt);
-  }
-  if (!ok) {
+  if (!bbh_joint_factor(L, 64, p, var[i], cross + i * p, s_cpp)) {
     scores[i] = NAN;
     return;
   }
   const double m0 = mean[i];
-  double mbar[QMAX];  // per-point sample means of the objective
+  double mbar[QMAX];  // per-point sample means of the objective: the draw at zbar
 #pragma unroll 1
-  for (int r = 0; r < q; r++) {
-    double y = (r == 0) ? m0 : s_mp[r - 1];
-    for (int c = 0; c <= r; c++) y = fma(L[tri(r, c) * 64], zbar[c], y);
-    mbar[r] = sign * y;
-  }
+  for (int r = 0; r < q; r++) mbar[r] = sign * bbh_joint_draw(L, 64, r, (r == 0) ? m0 : s_mp[r - 1], zbar);
   double sum = 0.0;
   for (int s = 0; s < S; s++) {
     const double* zs = z + (int64_t)s * q;
     double mx = -INFINITY;
 #pragma unroll 1
     for (int r = 0; r < q; r++) {
-      double y = (r == 0) ? m0 : s_mp[r - 1];
-      for (int c = 0; c <= r; c++) y = fma(L[tri(r, c) * 64], zs[c], y);
+      const double y = bbh_joint_draw(L, 64, r, (r == 0) ? m0 : s_mp[r - 1], zs);
       mx = fmax(mx, bbh_mc_utility(kind, sign * y, mbar[r], best_f, cu));
     }
     sum += mx;
@@ -1616,64 +1558,24 @@ __global__ __launch_bounds__(256) void bbh_mc_pending_q_kernel(int kind, const d
     return;
   }
   double L[Q * (Q + 1) / 2], A[Q * (Q + 1) / 2];
-  A[0] = var[i];
-#pragma unroll
-  for (int r = 1; r < Q; r++) {
-    A[r * (r + 1) / 2] = cross[i * P + (r - 1)];
-#pragma unroll
-    for (int c = 1; c <= r; c++) A[r * (r + 1) / 2 + c] = s_cpp[(r - 1) * P + (c - 1)];
-  }
-  double jitter = 0.0;
-  bool ok = false;
-  for (int attempt = 0; attempt < 4 && !ok; attempt++) {
-    ok = true;
-#pragma unroll
-    for (int r = 0; r < Q; r++) {
-#pragma unroll
-      for (int c = 0; c <= r; c++) {
-        double sacc = A[r * (r + 1) / 2 + c];
-        if (r == c) sacc += jitter;
-#pragma unroll
-        for (int k = 0; k < c; k++) sacc -= L[r * (r + 1) / 2 + k] * L[c * (c + 1) / 2 + k];
-        if (r == c) {
-          if (!(sacc > 0.0)) ok = false;
-          L[r * (r + 1) / 2 + r] = sqrt(sacc);
-        } else {
-          L[r * (r + 1) / 2 + c] = sacc / L[c * (c + 1) / 2 + c];
-        }
-      }
-    }
-    if (!ok) jitter = 1e-8 * pow(10.0, (double)attempt);
-  }
-  if (!ok) {
+  bbh_joint_load_q<Q>(A, var[i], cross + i * P, s_cpp);
+  if (!bbh_joint_factor_q<Q>(A, L)) {
     scores[i] = NAN;
     return;
   }
-  double m[Q], mbar[Q];
+  double m[Q], mbar[Q], y[Q];
   m[0] = mean[i];
 #pragma unroll
   for (int r = 1; r < Q; r++) m[r] = s_mp[r - 1];
+  bbh_joint_draw_q<Q>(L, m, s_zb, y);  // per-point sample means of the objective: the draw at zbar
 #pragma unroll
-  for (int r = 0; r < Q; r++) {
-    double y = m[r];
-#pragma unroll
-    for (int c = 0; c <= r; c++) y = fma(L[r * (r + 1) / 2 + c], s_zb[c], y);
-    mbar[r] = sign * y;
-  }
+  for (int r = 0; r < Q; r++) mbar[r] = sign * y[r];
   double sum = 0.0;
   for (int s = 0; s < S; s++) {
-    const double* zs = s_zq + (int64_t)s * Q;
-    double zr[Q];
-#pragma unroll
-    for (int c = 0; c < Q; c++) zr[c] = zs[c];
+    bbh_joint_draw_q<Q>(L, m, s_zq + (int64_t)s * Q, y);
     double mx = -INFINITY;
 #pragma unroll
-    for (int r = 0; r < Q; r++) {
-      double y = m[r];
-#pragma unroll
-      for (int c = 0; c <= r; c++) y = fma(L[r * (r + 1) / 2 + c], zr[c], y);
-      mx = fmax(mx, bbh_mc_utility(kind, sign * y, mbar[r], best_f, cu));
-    }
+    for (int r = 0; r < Q; r++) mx = fmax(mx, bbh_mc_utility(kind, sign * y[r], mbar[r], best_f, cu));
     sum += mx;
   }
   scores[i] = sum / (double)S;
@@ -1777,48 +1679,17 @@ extern "C" int bbh_mc_acq_pending(bbh_handle* h, int32_t kind, const double* mea
   }
   if (N == 0) return 0;
   BBH_HIP_TRY(h, hipSetDevice(h->device));
-  const int q = p + 1;
-  std::vector<double> buf((size_t)S * q + q + p + (size_t)p * p, 0.0);
-  memcpy(buf.data(), z_host, sizeof(double) * S * q);
-  double* zb = buf.data() + S * q;
-  for (int64_t s = 0; s < S; s++)
-    for (int c = 0; c < q; c++) zb[c] += z_host[s * q + c];
-  for (int c = 0; c < q; c++) zb[c] /= (double)S;
-  memcpy(zb + q, h->pend_mean.data(), sizeof(double) * p);
-  memcpy(zb + q + p, h->pend_cov.data(), sizeof(double) * p * p);
-  int rc = bbh_upload_z(h, buf.data(), buf.size());
+  bbh_joint_dev d;
+  const int rc = bbh_upload_joint(h, z_host, S, p, h->pend_mean.data(), h->pend_cov.data(), true, &d);
   if (rc) return rc;
-  const double* dz = h->d_z;
-  const double* dzb = dz + S * q;
-  const double* dmp = dzb + q;
-  const double* dcpp = dmp + p;
   const double cu = bbh_mc_cu(kind, beta);
-  const bool fits = sizeof(double) * buf.size() <= 60 * 1024;  // base samples in LDS
   bbh_timed_scope timed(h, BBH_TIMED_PENDING);
-#define BBH_MC_PENDING_Q(QV)                                                                                     \
-  case QV:                                                                                                       \
-    bbh_launch_mc_pending_q<QV>(h->stream, kind, mean_dev, var_dev, cross_dev, N, dmp, dcpp, dz, dzb, (int)S,    \
-                                best_f, sign, cu, alive_dev, scores_dev);                                        \
-    break;
-  switch (fits && !h->sw.pending_lds_form ? q : 0) {
-    BBH_MC_PENDING_Q(2)
-    BBH_MC_PENDING_Q(3)
-    BBH_MC_PENDING_Q(4)
-    BBH_MC_PENDING_Q(5)
-    BBH_MC_PENDING_Q(6)
-    BBH_MC_PENDING_Q(7)
-    BBH_MC_PENDING_Q(8)
-    BBH_MC_PENDING_Q(9)
-    BBH_MC_PENDING_Q(10)
-    BBH_MC_PENDING_Q(11)
-    BBH_MC_PENDING_Q(12)
-    BBH_MC_PENDING_Q(13)
-    BBH_MC_PENDING_Q(14)
-    default:
-      hipLaunchKernelGGL(bbh_mc_pending_kernel, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, h->stream, kind, mean_dev,
-                         var_dev, cross_dev, N, p, dmp, dcpp, dz, dzb, (int)S, best_f, sign, cu, alive_dev, scores_dev);
-  }
-#undef BBH_MC_PENDING_Q
+  if (!(bbh_fits_register_form(d.bytes) && !h->sw.pending_lds_form && bbh_dispatch_q(p + 1, [&](auto Q) {
+          bbh_launch_mc_pending_q<decltype(Q)::value>(h->stream, kind, mean_dev, var_dev, cross_dev, N, d.mean_p, d.cov_pp, d.z, d.zbar,
+                                                      (int)S, best_f, sign, cu, alive_dev, scores_dev);
+        })))
+    hipLaunchKernelGGL(bbh_mc_pending_kernel, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, h->stream, kind, mean_dev, var_dev,
+                       cross_dev, N, p, d.mean_p, d.cov_pp, d.z, d.zbar, (int)S, best_f, sign, cu, alive_dev, scores_dev);
   BBH_HIP_TRY(h, hipGetLastError());
   return 0;
 }
