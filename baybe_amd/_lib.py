@@ -147,6 +147,25 @@ SIGNATURES = {
                              C.c_void_p, C.c_void_p]),
     "bbh_score_nei": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, c_double_p, C.c_int64, C.c_void_p,
                                 C.c_double, C.c_void_p, C.c_void_p]),
+    "bbh_scalarized_best_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, c_double_p, c_double_p, c_double_p,
+                                          C.c_void_p]),
+    "bbh_scalarized_best_frequency_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, c_double_p, c_double_p,
+                                                    c_double_p, c_int64_p]),
+    "bbh_nparego_q1": (
+        C.c_int,
+        [C.c_void_p, C.c_int32, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), c_double_p, C.c_void_p, C.c_int64,
+         c_double_p, c_double_p, c_double_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    ),
+    "bbh_qnehvi_cells": (
+        C.c_int,
+        [C.c_void_p, C.c_int32, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), c_double_p, c_double_p,
+         C.c_int64, C.c_void_p, C.c_void_p],
+    ),
+    "bbh_qnehvi_sm": (
+        C.c_int,
+        [C.c_void_p, C.c_int32, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), c_double_p, c_double_p,
+         C.c_int64, c_int64_p, c_double_p, c_double_p, C.c_void_p, C.c_void_p],
+    ),
     "bbh_nehvi_samples": (C.c_int, [C.c_void_p, c_double_p, C.c_int64, C.c_int64, C.c_double, C.c_int32, C.c_int32, C.c_void_p, C.c_int32]),
     "bbh_nehvi_samples_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_double, C.c_int32, C.c_int32,
                                         C.c_void_p, C.c_int32]),

@@ -1,7 +1,8 @@
 """Declarative acquisition functions of the HIP path (mirror of ``baybe/acquisition/acqfs.py``).
 
 Only what the hot path scores on the device is defined: qLogEI (``acqfs.py:219-223``), the noisy forms qNEI / qLogNEI
-(``acqfs.py:226-243``), qLogNEHVI and the closed-form/posterior read-backs built from (mean, variance).  BoTorch's defaults that BayBE
+(``acqfs.py:226-243``), the noisy Pareto functions qLogNEHVI / qNEHVI (``acqfs.py:467-484``) and qLogNParEGO
+(``acqfs.py:328-336``), and the closed-form/posterior read-backs built from (mean, variance).  BoTorch's defaults that BayBE
 does not expose are recorded as explicit fields (sample count 512; fat=True, tau_relu=1e-6,
 tau_max=1e-2 are compiled into the kernels)."""
 
@@ -102,6 +103,7 @@ class qLogNoisyExpectedHypervolumeImprovement:
     """Logarithmic Monte-Carlo noisy expected hypervolume improvement (``acqfs.py:477-484``)."""
 
     abbreviation: ClassVar[str] = "qLogNEHVI"
+    kind: ClassVar[str] = "qLogNEHVI"
     supports_batching: ClassVar[bool] = True
     supports_pending_experiments: ClassVar[bool] = True
     supports_multi_output: ClassVar[bool] = True
@@ -119,6 +121,67 @@ class qLogNoisyExpectedHypervolumeImprovement:
 
 
 qLogNEHVI = qLogNoisyExpectedHypervolumeImprovement
+
+
+@define(frozen=True)
+class qNoisyExpectedHypervolumeImprovement:
+    """Monte-Carlo noisy expected hypervolume improvement (``acqfs.py:467-474``), scored by ``baybe_amd.nehvi.HipNEHVIPlain``."""
+
+    abbreviation: ClassVar[str] = "qNEHVI"
+    kind: ClassVar[str] = "qNEHVI"
+    supports_batching: ClassVar[bool] = True
+    supports_pending_experiments: ClassVar[bool] = True
+    supports_multi_output: ClassVar[bool] = True
+    is_mc: ClassVar[bool] = True
+    is_analytic: ClassVar[bool] = False
+
+    reference_point = field(default=None, converter=_convert_ref)
+    """As for qLogNEHVI."""
+
+    prune_baseline: bool = field(default=True, validator=instance_of(bool))
+    """Auto-prune baseline points that are unlikely to be Pareto-optimal."""
+
+    n_mc_samples: int = field(default=128, validator=[instance_of(int), ge(1)])
+    """Sobol base samples (BoTorch default for multi-objective MC acquisition functions)."""
+
+
+qNEHVI = qNoisyExpectedHypervolumeImprovement
+
+
+def _convert_weights(value):
+    return None if value is None else tuple(float(v) for v in value)
+
+
+@define(frozen=True)
+class qLogNParEGO:
+    """Pareto optimization via Chebyshev scalarization of the targets (``acqfs.py:328-336``), scored by
+    ``baybe_amd.nparego.HipNParEGO``."""
+
+    abbreviation: ClassVar[str] = "qLogNParEGO"
+    kind: ClassVar[str] = "qLogNParEGO"
+    supports_batching: ClassVar[bool] = True
+    supports_pending_experiments: ClassVar[bool] = True
+    supports_multi_output: ClassVar[bool] = True
+    is_mc: ClassVar[bool] = True
+    is_analytic: ClassVar[bool] = False
+
+    prune_baseline: bool = field(default=True, validator=instance_of(bool))
+    """Auto-prune baseline points that are unlikely to be the best of any joint posterior sample."""
+
+    n_mc_samples: int = field(default=512, validator=[instance_of(int), ge(1)])
+    """Sobol base samples (the single-output MC default that reaches qLogNEI's constructor; BayBE has no knob for it)."""
+
+    scalarization_weights = field(default=None, converter=_convert_weights)
+    """Weights on the simplex, one per target (BoTorch's argument of that name; BayBE has no knob for it).  None: drawn from
+    torch's global generator when the acquisition function is built (``sample_simplex``)."""
+
+    @scalarization_weights.validator
+    def _check_weights(self, _, value):
+        if value is not None and (any(not 0.0 <= v <= 1.0 for v in value) or abs(sum(value) - 1.0) > 1e-9):
+            raise ValueError(f"scalarization_weights must be non-negative and sum to 1, got {value!r}")
+
+
+_NOISY_PARETO = {c.abbreviation: c for c in (qLogNoisyExpectedHypervolumeImprovement, qNoisyExpectedHypervolumeImprovement, qLogNParEGO)}
 
 
 def _nei_class(name: str, abbr: str, doc: str):
@@ -146,7 +209,7 @@ _NOISY_EI = {c.abbreviation: c for c in (qNoisyExpectedImprovement, qLogNoisyExp
 
 def convert_acqf(acqf):
     """``baybe.acquisition.utils.convert_acqf``: accept abbreviations / BayBE objects."""
-    if acqf is None or isinstance(acqf, (qLogExpectedImprovement, qLogNoisyExpectedHypervolumeImprovement)):
+    if acqf is None or isinstance(acqf, (qLogExpectedImprovement, *_NOISY_PARETO.values())):
         return acqf
     if type(acqf) in _SINGLE_OUTPUT.values() or type(acqf) in _NOISY_EI.values():
         return acqf
@@ -163,14 +226,16 @@ def convert_acqf(acqf):
             return cls(**kw)
     if name in ("qLogEI", "qLogExpectedImprovement"):
         return qLogExpectedImprovement()
-    if name in ("qLogNEHVI", "qLogNoisyExpectedHypervolumeImprovement"):
-        kw = {}
-        if not isinstance(acqf, str):
-            kw = {"reference_point": getattr(acqf, "reference_point", None),
-                  "prune_baseline": getattr(acqf, "prune_baseline", True)}
-        return qLogNoisyExpectedHypervolumeImprovement(**kw)
+    for abbr, cls in _NOISY_PARETO.items():
+        if name in (abbr, cls.__name__):
+            kw = {}
+            if not isinstance(acqf, str):
+                kw = {"prune_baseline": getattr(acqf, "prune_baseline", True)}
+                if abbr != "qLogNParEGO":
+                    kw["reference_point"] = getattr(acqf, "reference_point", None)
+            return cls(**kw)
     from baybe_amd.exceptions import IncompatibleAcquisitionFunctionError
 
     raise IncompatibleAcquisitionFunctionError(
-        f"The HIP recommender scores the MC / analytic EI-PI-UCB-SR families, qNEI / qLogNEI and qLogNEHVI on the device; '{name}' is not available on this path."
+        f"The HIP recommender scores the MC / analytic EI-PI-UCB-SR families, qNEI / qLogNEI, qLogNEHVI / qNEHVI and qLogNParEGO on the device; '{name}' is not available on this path."
     )

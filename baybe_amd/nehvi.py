@@ -94,6 +94,8 @@ class HipNEHVI:
     """qLogNEHVI scorer over m independent HIP GPs (q = 1 t-batches, pending points cached into the
     baseline exactly as BoTorch's ``cache_pending=True``)."""
 
+    name = "qLogNEHVI"  # (the acquisition function a refusal speaks of)
+
     def __init__(self, engines, signs, X_baseline, ref_point, n_mc_samples: int = 128, prune_baseline: bool = True,
                  device: int = 0):
         if not 1 <= len(engines) <= _lib.MAX_OBJECTIVES:
@@ -103,7 +105,7 @@ class HipNEHVI:
             from baybe_amd.exceptions import IncompatibilityError
 
             # (the extended models condition on noise-free latent rows, which the RFF kernel's uniform-noise feature-space form does not have)
-            raise IncompatibilityError("qLogNEHVI (ParetoObjective) is not available with an RFFKernel surrogate on the HIP path.")
+            raise IncompatibilityError(f"{self.name} (ParetoObjective) is not available with an RFFKernel surrogate on the HIP path.")
         self.outputs = [_Output(e, HipGP(device), float(s)) for e, s in zip(engines, signs)]
         self.signs = np.asarray(signs, dtype=np.float64)
         self.X_baseline = np.ascontiguousarray(np.atleast_2d(X_baseline), dtype=np.float64)
@@ -394,6 +396,15 @@ class HipNEHVI:
         scores = torch.empty(N, dtype=torch.float64, device=X_dev.device)
         tp = (C.c_void_p * self.m)(*[t.data_ptr() for t in tmats])
         vp = (C.c_void_p * self.m)(*[v.data_ptr() for v in vars_])
+        self._score_cells(N, tp, vp, alive, scores)
+        if sync:
+            torch.cuda.synchronize(X_dev.device)  # tmats / vars_ must outlive the kernel
+        else:
+            self._keep = (tmats, vars_)  # (the caller synchronises; the operands live until the next pass)
+        return scores
+
+    def _score_cells(self, N, tp, vp, alive, scores):
+        """The cell kernel over the m sample-major blocks ``tp`` and variances ``vp`` (device cell lists, or the host form)."""
         h = self.outputs[0].ext
         sg = np.ascontiguousarray(self.signs)
         zx = np.ascontiguousarray(self.zx)
@@ -408,11 +419,6 @@ class HipNEHVI:
                 alive.data_ptr() if alive is not None else None, scores.data_ptr(),
             )
         h._check(rc, "bbh_qlognehvi")
-        if sync:
-            torch.cuda.synchronize(X_dev.device)  # tmats / vars_ must outlive the kernel
-        else:
-            self._keep = (tmats, vars_)  # (the caller synchronises; the operands live until the next pass)
-        return scores
 
     def greedy(self, X_dev, q: int, seed: int | None = None, prune_seed: int | None = None,
                X_pending: np.ndarray | None = None, alive=None, shard=None) -> GreedyResult:
@@ -450,3 +456,27 @@ class HipNEHVI:
             values.append(float(val))
             picks.append(np.asarray(row, dtype=np.float64).reshape(1, d))
         return GreedyResult(indices, values)
+
+
+class HipNEHVIPlain(HipNEHVI):
+    """qNoisyExpectedHypervolumeImprovement (``baybe/acquisition/acqfs.py:467-474``): qLogNEHVI's per-sample cells, samples, pruning,
+    reference point and greedy loop, scored as the plain mean over samples of the hypervolume improvement
+    ``sum_cells prod_o max(min(f_o - lo_o, len_o), 0)`` (``bbh_qnehvi_cells`` / ``bbh_qnehvi_sm``, double precision throughout)."""
+
+    name = "qNEHVI"
+
+    def _score_cells(self, N, tp, vp, alive, scores):
+        h = self.outputs[0].ext
+        sg = np.ascontiguousarray(self.signs)
+        zx = np.ascontiguousarray(self.zx)
+        alive_ptr = alive.data_ptr() if alive is not None else None
+        if self._cells_on_device:
+            rc = self._lib.bbh_qnehvi_cells(h._h, self.m, N, tp, vp, _dp(sg), _dp(zx), self.S, alive_ptr, scores.data_ptr())
+        else:
+            off = np.ascontiguousarray(self.cell_off, dtype=np.int64)
+            rc = self._lib.bbh_qnehvi_sm(
+                h._h, self.m, N, tp, vp, _dp(sg), _dp(zx), self.S, off.ctypes.data_as(_lib.c_int64_p),
+                _dp(self.cell_lo) if len(self.cell_lo) else None, _dp(self.cell_ll) if len(self.cell_ll) else None,
+                alive_ptr, scores.data_ptr(),
+            )
+        h._check(rc, "bbh_qnehvi")

@@ -226,25 +226,36 @@ class HipRecommenderImpl:
             self._pending_comp = np.ascontiguousarray(pend.to_numpy(dtype=np.float64))
         self._nehvi = None
         if _is_multi_output(objective):
-            from baybe_amd.nehvi import HipNEHVI, compute_ref_point
-
             models = surrogate.models
             signs = np.array([m.sign for m in models])
-            names = [t.name for t in objective.targets]
-            ref = acqf.reference_point
-            if not isinstance(ref, tuple):  # _builder.py:301-317: from completely measured rows
-                complete = measurements[names].dropna()
-                if complete.empty:
-                    raise ValueError(
-                        "For calculating a default reference point, at least one configuration must have a "
-                        "measured value for all targets. Set 'reference_point' explicitly."
-                    )
-                kw = {} if ref is None else {"factor": ref}
-                ref = compute_ref_point(complete.to_numpy(dtype=np.float64) * signs[None, :], **kw)
             X_base = np.ascontiguousarray(searchspace.transform(measurements, allow_extra=True).to_numpy(dtype=np.float64))
-            self._nehvi = HipNEHVI([m.engine for m in models], signs, X_base, np.asarray(ref, dtype=np.float64),
-                                   n_mc_samples=acqf.n_mc_samples, prune_baseline=acqf.prune_baseline,
-                                   device=models[0].engine.device)
+            if acqf.kind == "qLogNParEGO":
+                from baybe_amd.nparego import HipNParEGO, draw_scalarization_weights
+
+                # the weights are fixed when the acquisition function is built: before the scoring and pruning seeds are drawn
+                weights = acqf.scalarization_weights
+                if weights is None:
+                    weights = draw_scalarization_weights(len(models), self.shard.agree if self.shard is not None else None)
+                self._nehvi = HipNParEGO([m.engine for m in models], signs, X_base, weights, n_mc_samples=acqf.n_mc_samples,
+                                         prune_baseline=acqf.prune_baseline, device=models[0].engine.device)
+            else:  # the hypervolume kinds
+                from baybe_amd.nehvi import HipNEHVI, HipNEHVIPlain, compute_ref_point
+
+                names = [t.name for t in objective.targets]
+                ref = acqf.reference_point
+                if not isinstance(ref, tuple):  # _builder.py:301-317: from completely measured rows
+                    complete = measurements[names].dropna()
+                    if complete.empty:
+                        raise ValueError(
+                            "For calculating a default reference point, at least one configuration must have a "
+                            "measured value for all targets. Set 'reference_point' explicitly."
+                        )
+                    kw = {} if ref is None else {"factor": ref}
+                    ref = compute_ref_point(complete.to_numpy(dtype=np.float64) * signs[None, :], **kw)
+                scorer = HipNEHVIPlain if acqf.kind == "qNEHVI" else HipNEHVI
+                self._nehvi = scorer([m.engine for m in models], signs, X_base, np.asarray(ref, dtype=np.float64),
+                                     n_mc_samples=acqf.n_mc_samples, prune_baseline=acqf.prune_baseline,
+                                     device=models[0].engine.device)
             self._best_f = None
         elif acqf.kind in ("qNEI", "qLogNEI"):
             from baybe_amd.nei import HipNEI
@@ -462,7 +473,7 @@ class HipRecommenderImpl:
         _check_continuous_part(cont)
         acqf, surrogate = self._acqf_in_use, self._surrogate_model
         if self._nehvi is not None:
-            raise IncompatibilityError("Multi-output objectives and qNEI / qLogNEI in hybrid / continuous spaces are not on the HIP path; use BotorchRecommender.")
+            raise IncompatibilityError("Multi-output objectives (qLogNEHVI / qNEHVI / qLogNParEGO) and qNEI / qLogNEI in hybrid / continuous spaces are not on the HIP path; use BotorchRecommender.")
         if batch_size > 1 and not acqf.supports_batching:
             raise IncompatibleAcquisitionFunctionError(
                 f"The '{self.__class__.__name__}' only works with Monte Carlo acquisition functions for batch sizes > 1.")

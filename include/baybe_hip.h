@@ -28,6 +28,9 @@
  *   bbh_nei_q1 /             qLogNoisyExpectedImprovement, q' = 1, with  baybe/acquisition/_builder.py:319-324 (X_baseline,
  *   bbh_sample_best_dev /    prune_inferior_points                       prune_baseline)
  *   bbh_best_frequency_dev
+ *   bbh_nparego_q1 /         qLogNParEGO, q' = 1 (Chebyshev scalarisation baybe/acquisition/acqfs.py:328-336
+ *   bbh_scalarized_best(_frequency)_dev  of the targets under qLogNEI)
+ *   bbh_qnehvi_cells / _sm   qNoisyExpectedHypervolumeImprovement        baybe/acquisition/acqfs.py:467-474
  *
  * Conventions
  *  - extern "C"; every function returns 0 on success, <0 on error;
@@ -354,6 +357,37 @@ int bbh_nei_q1(bbh_handle* h, int32_t kind, const double* tmat_sm_dev, const dou
 int bbh_score_nei(bbh_handle* h, int32_t kind, const double* X_dev, int64_t N, int64_t ldx, const double* var_dev,
                   const double* zx_host, int64_t S, const double* best_dev, double sign, const uint8_t* alive_dev,
                   double* scores_dev);
+
+/* ---- qLogNParEGO (BoTorch qLogNParEGO; built like the noisy forms above, baybe/acquisition/_builder.py:319-324) --------------
+ * qLogNoisyExpectedImprovement of the augmented Chebyshev scalarisation of m oriented targets, q' = 1; picks and pending points
+ * join the baseline.  Set-up as for qLogNEHVI: one extended model per target, bbh_nehvi_samples wrote the oriented baseline
+ * samples Fb_dev [S, nb, m] and installed each target's S weight columns.  With w_host [m] weights on the simplex, hi_host [m] and
+ * inv_range_host [m] = 1 / (hi - lo) (bounds of the baseline's oriented posterior means):
+ *   t_o = w_o (hi_o - y_o) inv_range_o,   g(y) = -(max_o t_o + 0.05 sum_o t_o). */
+/* best_dev[s] = max_b g(Fb_dev[s, b, :]): the per-sample incumbent.  Asynchronous. */
+int bbh_scalarized_best_dev(bbh_handle* h, const double* Fb_dev, int64_t S, int64_t nb, int32_t m, const double* w_host,
+                            const double* hi_host, const double* inv_range_host, double* best_dev);
+/* prune_inferior_points under the scalarisation: counts_host[b] = number of the S samples in which point b has the largest g
+ * (ties: the first index).  Returns after the stream has drained. */
+int bbh_scalarized_best_frequency_dev(bbh_handle* h, const double* Fb_dev, int64_t S, int64_t nb, int32_t m, const double* w_host,
+                                      const double* hi_host, const double* inv_range_host, int64_t* counts_host);
+/* Scores of N candidates from the m sample-major blocks tmat_sm_dev[o] [S, N] (bbh_posterior_columns_sm of target o's handle) and
+ * variances var_dev[o] [N]:  f_s,o = sign_host[o] (tmat[o][s][i] + safe_sd(var[o][i]) zx_dev[s * m + o]),  u_s = g(f_s) - best_dev[s],
+ * scores_dev[i] = logmeanexp_s log_fatplus(u_s; 1e-6); rows with alive_dev[i] == 0 score -inf.  The sample axis is cut into slices
+ * of a fixed length whose partial sums are combined in a fixed order: a row's score does not depend on N (the caller chunks the
+ * candidates) and equal rows score bit-identically.  Workspace: S / 16 x N doubles on the handle.  Asynchronous. */
+int bbh_nparego_q1(bbh_handle* h, int32_t m, int64_t N, const double* const* tmat_sm_dev, const double* const* var_dev,
+                   const double* sign_host, const double* zx_dev, int64_t S, const double* w_host, const double* hi_host,
+                   const double* inv_range_host, const double* best_dev, const uint8_t* alive_dev, double* scores_dev);
+
+/* ---- qNoisyExpectedHypervolumeImprovement (plain) ----------------------------------------------------------------------------
+ * The operands of bbh_qlognehvi_cells / bbh_qlognehvi_sm, scored without smoothing, in double precision:
+ * scores_dev[i] = (1/S) sum_s sum_{cells c of s} prod_o max(min(f_s,o - lo_c,o, len_c,o), 0); rows with alive_dev[i] == 0 score -inf. */
+int bbh_qnehvi_cells(bbh_handle* h, int32_t m, int64_t N, const double* const* tmat_dev, const double* const* var_dev,
+                     const double* sign_host, const double* zx_host, int64_t S, const uint8_t* alive_dev, double* scores_dev);
+int bbh_qnehvi_sm(bbh_handle* h, int32_t m, int64_t N, const double* const* tmat_dev, const double* const* var_dev,
+                  const double* sign_host, const double* zx_host, int64_t S, const int64_t* cell_off_host, const double* cell_lo_host,
+                  const double* cell_loglen_host, const uint8_t* alive_dev, double* scores_dev);
 
 /* Box decomposition of the non-dominated region, one per MC sample (host code, no device work; BoTorch's
  * FastNondominatedPartitioning inside qLogNoisyExpectedHypervolumeImprovement, built at
