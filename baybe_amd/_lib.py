@@ -44,6 +44,12 @@ class ModelDesc(C.Structure):
     ]
 
 
+class ObjectiveProg(C.Structure):
+    """``bbh_objective_prog`` (include/baybe_hip.h): a target transformation as at most 8 scalar operations."""
+
+    _fields_ = [("n_ops", C.c_int32), ("op", C.c_int32 * 8), ("p", (C.c_double * 3) * 8)]
+
+
 KERNEL_KINDS = {"matern12": 0, "matern32": 1, "matern52": 2, "rbf": 3,
                 "piecewise0": 4, "piecewise1": 5, "piecewise2": 6, "piecewise3": 7, "rq": 8,
                 "linear": 9, "poly1": 10, "poly2": 11, "poly3": 12, "poly4": 13, "periodic": 14, "rff": 15}  # enum bbh_kernel_kind
@@ -133,6 +139,16 @@ SIGNATURES = {
         C.c_int,
         [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, c_double_p, C.c_int64, C.c_double,
          C.c_double, C.c_double, C.c_void_p, C.c_void_p],
+    ),
+    "bbh_mc_acq_obj_q1": (
+        C.c_int,
+        [C.c_void_p, C.c_int32, C.POINTER(ObjectiveProg), C.c_void_p, C.c_void_p, C.c_int64, c_double_p, C.c_int64, C.c_double,
+         C.c_double, C.c_void_p, C.c_void_p],
+    ),
+    "bbh_mc_acq_obj_pending": (
+        C.c_int,
+        [C.c_void_p, C.c_int32, C.POINTER(ObjectiveProg), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, c_double_p,
+         c_double_p, c_double_p, C.c_int64, C.c_double, C.c_double, C.c_void_p, C.c_void_p],
     ),
     "bbh_analytic_acq": (
         C.c_int,

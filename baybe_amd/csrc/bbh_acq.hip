@@ -8,7 +8,7 @@
 //
 // The kernels that score a candidate jointly with p pending points (bbh_qlogei_pending_q_kernel, bbh_qlogei_pending_kernel,
 // bbh_qlogei_pending_big_kernel, bbh_mc_pending_q_kernel, bbh_mc_pending_kernel) share one core, "shared core of the joint
-// q'-batch kernels" below: Sigma = [[v0, c^T], [c, cov_pp]], its Cholesky factor with the jitter ladder, and the draw
+// q'-batch kernels" (strided form: bbh_joint.h, also under bbh_objacq.hip; register form: below): Sigma = [[v0, c^T], [c, cov_pp]], its Cholesky factor with the jitter ladder, and the draw
 // y = m + L z, once for a factor in strided memory (LDS or the global workspace) and once for a factor in registers.  A kernel
 // adds its storage and its utility; the host side shares the upload, the 60 KB rule and the Q = 2 ... 14 dispatch.
 #include <math.h>
@@ -65,61 +65,7 @@ __global__ __launch_bounds__(256) void bbh_qlogei_q1_kernel(const double* __rest
   scores[i] = log(TAU_RELU) + log(sum) - log((double)S);
 }
 
-// ---- shared core of the joint q'-batch kernels ----------------------------------------------------------------------------
-// q' = 1 + p points: the candidate, then the p pending points.  Per candidate: Sigma = [[v0, c^T], [c, cov_pp]] (v0 = var[i],
-// c = cross[i p ...]), its Cholesky factor with exact psd_safe_cholesky semantics - diagonal jitter 0, 1e-8, 1e-7, 1e-6, a pivot
-// !(s > 0) ends an attempt, no factor after the fourth (gpytorch raises NotPSDError; the kernels score NaN) - and per base sample
-// the draw y_r = m_r + sum_c L_rc z_c.  The factor is thread-private, packed lower-triangular (element (r, c) at tri(r, c)), and
-// these three pieces are written once per storage class:
-//   strided memory, run-time q'  element e at L[e * stride]: stride 64 in LDS (bbh_qlogei_pending_kernel, bbh_mc_pending_kernel),
-//                                stride N in a global workspace (bbh_qlogei_pending_big_kernel); a failed pivot breaks out
-//   registers, template <int Q>  every index a compile-time constant (bbh_qlogei_pending_q_kernel, bbh_mc_pending_q_kernel);
-//                                a failed pivot lets the attempt run on and discards it
-// Both factor row by row with the k loop subtracting in ascending order, and draw by fma in ascending c from the mean.
-#define QMAX 16
-#define QTRI (QMAX * (QMAX + 1) / 2)
-__device__ __forceinline__ int tri(int i, int j) { return i * (i + 1) / 2 + j; }
-
-template <typename ST>  // ST: type of the stride (int 64, int64_t N)
-__device__ __forceinline__ bool bbh_joint_factor(double* L, ST stride, int p, double v0, const double* cross_i, const double* cov_pp) {
-  const int q = p + 1;
-  double jitter = 0.0;
-  bool ok = false;
-  for (int attempt = 0; attempt < 4 && !ok; attempt++) {
-    ok = true;
-    for (int r = 0; r < q && ok; r++) {
-      for (int c = 0; c <= r; c++) {
-        double s;
-        if (r == 0)
-          s = v0;
-        else if (c == 0)
-          s = cross_i[r - 1];
-        else
-          s = cov_pp[(r - 1) * p + (c - 1)];
-        if (r == c) s += jitter;
-        for (int k = 0; k < c; k++) s -= L[tri(r, k) * stride] * L[tri(c, k) * stride];
-        if (r == c) {
-          if (!(s > 0.0)) {
-            ok = false;
-            break;
-          }
-          L[tri(r, r) * stride] = sqrt(s);
-        } else {
-          L[tri(r, c) * stride] = s / L[tri(c, c) * stride];
-        }
-      }
-    }
-    if (!ok) jitter = 1e-8 * pow(10.0, (double)attempt);
-  }
-  return ok;
-}
-
-template <typename ST>
-__device__ __forceinline__ double bbh_joint_draw(const double* L, ST stride, int r, double m, const double* zs) {
-  double y = m;
-  for (int c = 0; c <= r; c++) y = fma(L[tri(r, c) * stride], zs[c], y);
-  return y;
-}
+#include "bbh_joint.h"  // shared core of the joint q'-batch kernels: QMAX, tri, bbh_joint_factor, bbh_joint_draw, bbh_upload_joint
 
 // qLogEI of one candidate from its strided factor: per sample li_r = log_fatplus(sign y_r - best_f), the fat maximum over the q'
 // points, a streaming log-sum-exp over the samples.  li: q' doubles of this thread, element r at li[r * li_stride].
@@ -617,34 +563,6 @@ int bbh_qlogei_q1_rounds(bbh_handle* h, const double* mean_dev, const double* va
   hipLaunchKernelGGL(bbh_qlogei_q1_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), sizeof(double) * S, h->stream,
                      mean_dev, var_dev, N, h->d_z, (int)S, best_f, sign, alive_dev, scores_dev);
   BBH_HIP_TRY(h, hipGetLastError());
-  return 0;
-}
-
-// One upload per joint launch: [z [S, q'] | zbar [q'] (column means of z: the MC family only) | mean_p [p] | cov_pp [p, p]]
-struct bbh_joint_dev {
-  const double *z, *zbar, *mean_p, *cov_pp;
-  size_t bytes;  // of the whole upload
-};
-static int bbh_upload_joint(bbh_handle* h, const double* z_host, int64_t S, int64_t p, const double* mp_host, const double* cpp_host,
-                            bool with_zbar, bbh_joint_dev* d) {
-  const int64_t q = p + 1, nzb = with_zbar ? q : 0;
-  std::vector<double> buf((size_t)S * q + nzb + p + (size_t)p * p, 0.0);
-  memcpy(buf.data(), z_host, sizeof(double) * S * q);
-  double* zb = buf.data() + S * q;
-  if (with_zbar) {
-    for (int64_t s = 0; s < S; s++)
-      for (int c = 0; c < q; c++) zb[c] += z_host[s * q + c];
-    for (int c = 0; c < q; c++) zb[c] /= (double)S;
-  }
-  memcpy(zb + nzb, mp_host, sizeof(double) * p);
-  memcpy(zb + nzb + p, cpp_host, sizeof(double) * p * p);
-  const int rc = bbh_upload_z(h, buf.data(), buf.size());
-  if (rc) return rc;
-  d->z = h->d_z;
-  d->zbar = with_zbar ? d->z + S * q : nullptr;
-  d->mean_p = d->z + S * q + nzb;
-  d->cov_pp = d->mean_p + p;
-  d->bytes = sizeof(double) * buf.size();
   return 0;
 }
 
@@ -1458,16 +1376,6 @@ extern "C" int bbh_pareto_frequency_dev(bbh_handle* h, const double* obj_dev, in
 // inputs.  MC family (BoTorch SampleReducingMCAcquisitionFunction): mean_s max_j u(obj_sj);
 // analytic family: closed forms in (mu~, sigma), sigma^2 clamped at 1e-12 as BoTorch does.
 // =================================================================================================
-__device__ __forceinline__ double bbh_mc_utility(int kind, double obj, double m, double best_f, double cu) {
-  switch (kind) {
-    case BBH_ACQ_QEI: return fmax(obj - best_f, 0.0);
-    case BBH_ACQ_QPI: return 1.0 / (1.0 + exp(-(obj - best_f) * 1e3));
-    case BBH_ACQ_QSR: return obj;
-    case BBH_ACQ_QUCB: return m + cu * fabs(obj - m);
-    default: return cu * fabs(obj - m);  // QPSTD
-  }
-}
-
 __global__ __launch_bounds__(256) void bbh_mc_q1_kernel(int kind, const double* __restrict__ mean, const double* __restrict__ var,
                                                         int64_t N, const double* __restrict__ z, int S, double zbar,
                                                         double best_f, double sign, double cu,
@@ -1633,12 +1541,6 @@ __global__ void bbh_analytic_kernel(int kind, const double* __restrict__ mean, c
       out = log(sd) + bbh_log_h(u);  // LogEI
   }
   scores[i] = out;
-}
-
-static double bbh_mc_cu(int kind, double beta) {
-  if (kind == BBH_ACQ_QUCB) return sqrt(beta * 3.141592653589793 / 2.0);
-  if (kind == BBH_ACQ_QPSTD) return sqrt(3.141592653589793 / 2.0);
-  return 0.0;
 }
 
 extern "C" int bbh_mc_acq_q1(bbh_handle* h, int32_t kind, const double* mean_dev, const double* var_dev, int64_t N,

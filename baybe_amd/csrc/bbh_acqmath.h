@@ -42,6 +42,24 @@ __device__ __forceinline__ double bbh_safe_sd(double v) {
   return sqrt(fmax(v, 0.0));
 }
 
+// ---- MC family (BoTorch SampleReducingMCAcquisitionFunction): the utility of one objective sample; m: the sample mean of the
+// objective (qUCB / qPSTD), cu: bbh_mc_cu ------------------------------------------------------------------------------------
+__device__ __forceinline__ double bbh_mc_utility(int kind, double obj, double m, double best_f, double cu) {
+  switch (kind) {
+    case BBH_ACQ_QEI: return fmax(obj - best_f, 0.0);
+    case BBH_ACQ_QPI: return 1.0 / (1.0 + exp(-(obj - best_f) * 1e3));
+    case BBH_ACQ_QSR: return obj;
+    case BBH_ACQ_QUCB: return m + cu * fabs(obj - m);
+    default: return cu * fabs(obj - m);  // QPSTD
+  }
+}
+
+static inline double bbh_mc_cu(int kind, double beta) {
+  if (kind == BBH_ACQ_QUCB) return sqrt(beta * 3.141592653589793 / 2.0);
+  if (kind == BBH_ACQ_QPSTD) return sqrt(3.141592653589793 / 2.0);
+  return 0.0;
+}
+
 // ---- qNEI / qLogNEI (bbh_nei.hip) ----------------------------------------------------------------
 // One MC sample of a candidate: the joint draw f_s = E[f(x) | D, F_b,s] + sd z_x,s against the sample's best baseline
 // value, u_s = sign f_s - best_s.  LOG: fatplus(u_s; tau_relu) / tau_relu (summed in the linear domain like

@@ -749,8 +749,11 @@ class HipGP:
         self._check(self._lib.bbh_train_posterior_mean(self._h, _dp(out)), "bbh_train_posterior_mean")
         return out
 
-    def best_f(self, sign: float = 1.0) -> float:
-        """max_i objective(posterior mean at x_i)  (baybe/acquisition/_builder.py:141-161,256-265)."""
+    def best_f(self, sign: float = 1.0, objective=None) -> float:
+        """max_i objective(posterior mean at x_i)  (baybe/acquisition/_builder.py:141-161,256-265); ``objective``: an
+        ``ObjectiveProgram`` in place of ``sign``."""
+        if objective is not None:
+            return float(objective.apply(self.train_posterior_mean()).max())
         return float((sign * self.train_posterior_mean()).max())
 
     # ---- qLogEI ---------------------------------------------------------------------------
@@ -789,14 +792,37 @@ class HipGP:
         return scores, vals, idx
 
     def mc_acq(self, kind: str, mean, var, z: np.ndarray, best_f: float = 0.0, sign: float = 1.0, beta: float = 0.2,
-               alive=None, cross=None):
-        """MC acquisition values (qLogEI, qEI, qPI, qSR, qUCB, qPSTD) of N t-batches [x_i ; pending]."""
+               alive=None, cross=None, objective=None, stats=None):
+        """MC acquisition values (qLogEI, qEI, qPI, qSR, qUCB, qPSTD) of N t-batches [x_i ; pending].  ``objective`` (a
+        ``baybe_amd.objective.ObjectiveProgram``) replaces ``sign``: every posterior sample passes through the program before the
+        utility (``bbh_mc_acq_obj_q1`` / ``bbh_mc_acq_obj_pending``); with ``cross`` the pending statistics are ``stats`` =
+        (mean [p], cov [p, p]), by default what the last ``set_pending`` returned."""
         torch = self._torch()
         z = np.ascontiguousarray(z, dtype=np.float64)
         N = mean.shape[0]
         scores = torch.empty(N, dtype=torch.float64, device=mean.device)
         k = _lib.ACQ_KINDS[kind]
         al = alive.data_ptr() if alive is not None else None
+        if objective is not None:
+            prog = objective.to_struct()
+            if cross is None:
+                z = z.reshape(-1)
+                rc = self._lib.bbh_mc_acq_obj_q1(self._h, k, C.byref(prog), mean.data_ptr(), var.data_ptr(), N, _dp(z), z.shape[0],
+                                                 float(best_f), float(beta), al, scores.data_ptr())
+            else:
+                stats = stats if stats is not None else getattr(self, "_pend_stats", None)
+                if stats is None:
+                    raise ValueError("no pending points set: call set_pending() or pass stats=(mean, cov)")
+                mp, cpp = stats
+                mp, cpp = np.ascontiguousarray(mp, dtype=np.float64), np.ascontiguousarray(cpp, dtype=np.float64)
+                p = mp.shape[0]
+                if not 1 <= p <= MAX_PENDING or cross.shape[1] != p or z.ndim != 2 or z.shape[1] != p + 1:
+                    raise ValueError(f"an objective program is scored jointly with 1 ... {MAX_PENDING} pending points")
+                rc = self._lib.bbh_mc_acq_obj_pending(self._h, k, C.byref(prog), mean.data_ptr(), var.data_ptr(), cross.data_ptr(), N,
+                                                      p, _dp(mp), _dp(cpp), _dp(z), z.shape[0], float(best_f), float(beta), al,
+                                                      scores.data_ptr())
+            self._check(rc, "bbh_mc_acq_obj")
+            return scores
         if cross is None:
             z = z.reshape(-1)
             rc = self._lib.bbh_mc_acq_q1(self._h, k, mean.data_ptr(), var.data_ptr(), N, _dp(z), z.shape[0], float(best_f),
@@ -846,6 +872,7 @@ class HipGP:
         """Pending points = base pending + greedy picks (candidate first, then pending)."""
         if X_pending is None or len(X_pending) == 0:
             self._check(self._lib.bbh_pending_set(self._h, None, 0, None, None), "bbh_pending_set")
+            self._pend_stats = None
             return None, None
         P = np.ascontiguousarray(X_pending, dtype=np.float64)
         p = P.shape[0]
@@ -855,6 +882,7 @@ class HipGP:
         cpp = np.empty((p, p))
         self._check(self._lib.bbh_pending_set(self._h, _dp(P), p, _dp(mp), _dp(cpp)), "bbh_pending_set")
         self._p = p
+        self._pend_stats = (mp, cpp)  # (what ``mc_acq(..., objective=...)`` hands to the joint kernel)
         return mp, cpp
 
     def cross_cov(self, X):
@@ -1041,6 +1069,7 @@ class HipGP:
         beta: float = 0.2,
         alive=None,
         speculate: bool = True,
+        objective=None,
     ) -> GreedyResult:
         """Sequential greedy of ``optimize_acqf_discrete(acqf, q, choices, unique=True)``.
 
@@ -1050,6 +1079,8 @@ class HipGP:
         ``shard`` (a ``baybe_amd.distributed.RowShard``) makes every selection a global one: the
         local winner is all-gathered (score, global index, row) and the global first-index argmax
         wins on every rank.
+        ``objective`` (an ``ObjectiveProgram``, in place of ``sign``): every step is one ``mc_acq`` call with the program - no
+        fused first step, no speculative statistics, at most 15 pending points.
         """
         torch = self._torch()
         X = self._as_dev(X)
@@ -1058,7 +1089,8 @@ class HipGP:
         if seed is None and z_by_q is None:
             seed = draw_sampler_seed()
         if best_f is None:
-            best_f = self.best_f(sign)
+            best_f = self.best_f(sign) if objective is None else self.best_f(1.0, objective)
+        okw = {} if objective is None else {"objective": objective}  # (an engine double without the feature is called as before)
         base = np.zeros((0, d)) if X_pending is None or len(X_pending) == 0 else np.atleast_2d(np.asarray(X_pending, dtype=np.float64))
         alive = torch.ones(N, dtype=torch.uint8, device=X.device) if alive is None else alive.clone()
         mean = var = None
@@ -1089,15 +1121,17 @@ class HipGP:
                 if mean is None:  # first step: posterior of every candidate, cached for the later steps
                     self.set_pending(None)
                     mean, var = self.posterior(X)
-                if kind == "qLogEI" and shard is None and N > 0:
+                if kind == "qLogEI" and shard is None and N > 0 and objective is None:
                     # scores, the winner and (for later steps) the head of the ranking in ONE call
                     m_spec = min(MAX_PENDING - b0, N, 4 * q) if (q > 1 and speculate and N > 1 and b0 < MAX_PENDING) else 1
                     scores, first_vals, first_top = self.qlogei_topk(mean, var, z[:, 0], best_f, sign, max(1, m_spec), alive)
                 else:
-                    scores = self.mc_acq(kind, mean, var, z[:, 0], best_f, sign, beta, alive)
+                    scores = self.mc_acq(kind, mean, var, z[:, 0], best_f, sign, beta, alive, **okw)
             else:
                 if mean is None:
                     mean, var = self.posterior(X)
+                if p > MAX_PENDING and objective is not None:
+                    raise ValueError(f"joint q-batches beyond {MAX_PENDING + 1} points are not available with a transformed target")
                 if p > MAX_PENDING:
                     # more than 15 pending points (the reference has no cap): columns of earlier steps are kept, the new pick's
                     # column comes from a one-point pass; the joint kernel takes the pending statistics explicitly
@@ -1116,7 +1150,7 @@ class HipGP:
                     if cross_spec is not None:
                         cols = [spec_pos.get(ix) for ix in indices]
                         cols = None if any(c is None for c in cols) else list(range(b0)) + cols
-                    if cols is not None and kind == "qLogEI" and spec_stats is not None:
+                    if cols is not None and kind == "qLogEI" and spec_stats is not None and objective is None:
                         # columns AND pending statistics are sub-blocks of what the speculative pass left: no bbh_pending_set
                         # round trip (0.15 - 0.3 ms of host work per step)
                         cross = cross_spec[:, cols].contiguous() if len(cols) != cross_spec.shape[1] else cross_spec
@@ -1129,7 +1163,7 @@ class HipGP:
                             cross = cross_spec[:, cols].contiguous() if len(cols) != cross_spec.shape[1] else cross_spec
                         else:
                             cross = self.cross_cov(X)
-                        scores = self.mc_acq(kind, mean, var, z, best_f, sign, beta, alive, cross=cross)
+                        scores = self.mc_acq(kind, mean, var, z, best_f, sign, beta, alive, cross=cross, **okw)
                     if p == MAX_PENDING:
                         big_cross = cross  # the next step continues from these columns
             step0_global = None

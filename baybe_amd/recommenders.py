@@ -91,12 +91,14 @@ def _is_multi_output(objective) -> bool:
     return bool(flag) if flag is not None else len(objective.targets) > 1
 
 
-def _check_objective(objective, acqf) -> None:
-    """What of ``baybe.objectives`` is on the device path, checked before anything is fitted: single targets and
-    Pareto stacking of identity / negated targets.  A ``DesirabilityObjective`` is
-    single-output in the reference (scalarised, optimised with qLogEI, ``objectives/desirability.py:222-265``) -
-    treating it as Pareto because it has several targets would answer a different question."""
+def _check_objective(objective, acqf):
+    """What of ``baybe.objectives`` is on the device path, checked before anything is fitted: single targets, with their
+    transformation as an objective program (``baybe_amd.objective``), and Pareto stacking of identity / negated targets (SURVEY.md
+    §8a row a9).  A ``DesirabilityObjective`` is single-output in the reference (scalarised, optimised with qLogEI,
+    ``objectives/desirability.py:222-265``) - treating it as Pareto because it has several targets would answer a different
+    question.  Returns the single target's ``ObjectiveProgram`` (None: identity, on the kernels' ``sign`` path)."""
     kind = type(objective).__name__
+    from baybe_amd.objective import objective_program
     from baybe_amd.surrogates import _target_sign, modeled_quantities
 
     quantities = modeled_quantities(objective)
@@ -117,8 +119,19 @@ def _check_objective(objective, acqf) -> None:
             f"The acquisition function '{type(acqf).__name__}' needs a multi-output objective, but a single-target "
             f"objective was given."
         )
-    for target in quantities:  # identity transformations (+ minimisation) only: raises IncompatibilityError
-        _target_sign(target)
+    if _is_multi_output(objective) or getattr(acqf, "kind", None) in ("qNEI", "qLogNEI"):
+        for target in quantities:  # identity transformations (+ minimisation) only: raises IncompatibilityError
+            _target_sign(target)
+        return None
+    program = objective_program(quantities[0])  # raises IncompatibilityError for what the kernels do not evaluate
+    if program is not None and getattr(acqf, "is_analytic", False) and program.as_affine() is None:
+        # only an affine map keeps the posterior Gaussian (posterior transform, objectives/single.py:77-91; _builder.py:224-234)
+        raise IncompatibilityError(
+            f"The selected analytical acquisition function '{type(acqf).__name__}' is incompatible with the assigned objective "
+            f"'{kind}' because the former requires a Gaussian distribution and the latter is configured to produce "
+            f"non-Gaussian outcomes."
+        )
+    return program
 
 
 def _check_continuous_part(cont) -> None:
@@ -213,7 +226,7 @@ class HipRecommenderImpl:
             _check_continuous_part(cont)  # hybrid / continuous spaces: box-bounded continuous parameters only
         self._objective = objective
         acqf = self._get_acquisition_function(objective, acquisition_function)
-        _check_objective(objective, acqf)
+        self._program = _check_objective(objective, acqf)
         self._acqf_in_use = acqf
         if pending_experiments is not None and not acqf.supports_pending_experiments:
             raise IncompatibleAcquisitionFunctionError(
@@ -262,11 +275,13 @@ class HipRecommenderImpl:
 
             # the noisy forms have no incumbent value: the baseline (all training inputs, _builder.py:319-324) is sampled instead
             X_base = np.ascontiguousarray(searchspace.transform(measurements, allow_extra=True).to_numpy(dtype=np.float64))
-            self._nehvi = HipNEI(surrogate.engine, surrogate.sign, X_base, n_mc_samples=acqf.n_mc_samples,
+            self._nehvi = HipNEI(surrogate.engine, self._sign(surrogate), X_base, n_mc_samples=acqf.n_mc_samples,
                                  prune_baseline=acqf.prune_baseline, log=acqf.kind == "qLogNEI", device=surrogate.engine.device)
             self._best_f = None
         else:
-            self._best_f = surrogate.engine.best_f(surrogate.sign)  # _builder.py:141-161, 256-265
+            # _builder.py:141-161, 256-265: the transformed posterior mean at the training inputs
+            eng = surrogate.engine
+            self._best_f = eng.best_f(surrogate.sign) if self._program is None else eng.best_f(1.0, self._program)
         return surrogate, acqf
 
     def _check_batch_size(self, batch_size, pending_experiments=None) -> None:
@@ -280,8 +295,9 @@ class HipRecommenderImpl:
                                  or getattr(acqf, "kind", None) in ("qNEI", "qLogNEI")):
             return
         # qLogEI: up to 64 points (beyond 16 through bbh_qlogei_pending_big, the factor in a global workspace); the other MC
-        # acquisition functions: 16
-        cap = (_lib.MAX_PENDING_BIG if getattr(acqf, "kind", None) == "qLogEI" else _lib.MAX_PENDING) + 1
+        # acquisition functions, and every one under an objective program (bbh_mc_acq_obj_pending): 16
+        big = getattr(acqf, "kind", None) == "qLogEI" and self._program is None
+        cap = (_lib.MAX_PENDING_BIG if big else _lib.MAX_PENDING) + 1
         if batch_size + n_pend > cap:
             raise IncompatibilityError(
                 f"batch_size ({batch_size}) + pending experiments ({n_pend}) exceeds {cap}, the largest "
@@ -297,6 +313,7 @@ class HipRecommenderImpl:
             raise NotImplementedError("Recommenders of type 'BayesianRecommender' do not support empty training data.")
         self._acqf_in_use = self._get_acquisition_function(objective)
         self._pending_comp = None
+        self._program = _check_objective(objective, self._acqf_in_use)  # (decides the batch-size cap)
         self._check_batch_size(batch_size, pending_experiments)  # before the fit
         self._setup_botorch_acqf(searchspace, objective, measurements, pending_experiments)
         return self._recommend_with_discrete_parts(searchspace, batch_size, pending_experiments=pending_experiments)
@@ -384,6 +401,10 @@ class HipRecommenderImpl:
             alive = torch.from_numpy(mask).to(Xd.device)
         return Xd, alive, labels
 
+    def _sign(self, surrogate) -> float:
+        """The ``sign`` argument of the kernels: the target's orientation, or +1 where an objective program carries it."""
+        return 1.0 if self._program is not None else surrogate.sign
+
     @property
     def _engine(self):
         model = self._surrogate_model
@@ -414,7 +435,7 @@ class HipRecommenderImpl:
         if acqf.is_analytic:  # q = 1 by construction (supports_batching is False)
             eng = surrogate.engine
             mean, var = eng.posterior(Xd)
-            scores = self._analytic_scores(eng, acqf, mean, var, surrogate.sign, alive)
+            scores = self._analytic_scores(eng, acqf, mean, var, self._sign(surrogate), alive)
             val, idx = eng.argmax(scores)
             if self.shard is not None:
                 val, idx, _ = self.shard.global_argmax(val, idx, Xd)
@@ -423,9 +444,9 @@ class HipRecommenderImpl:
             res = GreedyResult([int(idx)], [float(val)])
         else:
             res = surrogate.engine.greedy_qlogei(
-                Xd, batch_size, S=acqf.n_mc_samples, seed=self._sampler_seed(), sign=surrogate.sign,
+                Xd, batch_size, S=acqf.n_mc_samples, seed=self._sampler_seed(), sign=self._sign(surrogate),
                 X_pending=self._pending_comp, best_f=self._best_f, shard=self.shard, kind=acqf.kind,
-                beta=getattr(acqf, "beta", 0.2), alive=alive,
+                beta=getattr(acqf, "beta", 0.2), alive=alive, **({} if self._program is None else {"objective": self._program}),
             )
         idxs = labels[np.asarray(res.indices, dtype=np.int64)]
         return (idxs, res) if return_values else idxs
@@ -512,12 +533,12 @@ class HipRecommenderImpl:
         picks, pick_labels = [], []
         for _step in range(batch_size):
             pend = np.vstack([base] + picks) if picks else base
-            scores = self._mc_or_analytic(eng, acqf, X, mean, var, pend, seed, surrogate.sign)
+            scores = self._mc_or_analytic(eng, acqf, X, mean, var, pend, seed, self._sign(surrogate))
             k = int(min(self.n_restarts, X.shape[0], 64))  # (bbh_topk returns at most 64 rows; the reference's n_restarts has no cap)
             _, top = eng.topk(scores, k)
             top = [int(t) for t in top if t >= 0]
             starts = X[torch.as_tensor(top, device=X.device)].cpu().numpy()
-            best_row, _ = self._compass_refine(eng, acqf, starts, dd, cb, pend, seed, surrogate.sign, iters=min(96, 24 + 8 * dc))
+            best_row, _ = self._compass_refine(eng, acqf, starts, dd, cb, pend, seed, self._sign(surrogate), iters=min(96, 24 + 8 * dc))
             picks.append(best_row.reshape(1, -1))
             if has_disc:  # the label of the refined winner's discrete part (copied bit for bit from its start row)
                 pick_labels.append(labels[int(np.nonzero((D == best_row[:dd]).all(axis=1))[0][0])])
@@ -593,6 +614,10 @@ class HipRecommenderImpl:
         return cur[i], float(val[i])
 
     def _analytic_scores(self, eng, acqf, mean, var, sign, alive=None):
+        if self._program is not None:
+            # an affine objective is the reference's posterior transform (objectives/single.py:77-91): N(a mu + b, a^2 sigma^2)
+            a, b = self._program.as_affine()
+            mean, var, sign = a * mean + b, (a * a) * var, 1.0
         return eng.analytic_acq(acqf.kind, mean, var, self._best_f, sign, getattr(acqf, "beta", 0.2),
                                 getattr(acqf, "maximize", True), alive)
 
@@ -614,8 +639,8 @@ class HipRecommenderImpl:
         if acqf.is_analytic:
             if len(pend):
                 raise IncompatibleAcquisitionFunctionError("Analytic acquisition functions score single points only.")
-            return float(self._analytic_scores(eng, acqf, mean, var, surrogate.sign).cpu().numpy()[0])
-        s = self._mc_scores_with_pending(eng, acqf, comp[:1], mean, var, pend, seed, surrogate.sign)
+            return float(self._analytic_scores(eng, acqf, mean, var, self._sign(surrogate)).cpu().numpy()[0])
+        s = self._mc_scores_with_pending(eng, acqf, comp[:1], mean, var, pend, seed, self._sign(surrogate))
         return float(s.cpu().numpy()[0])
 
     def _mc_scores_with_pending(self, eng, acqf, comp, mean, var, pend, seed, sign):
@@ -623,11 +648,17 @@ class HipRecommenderImpl:
         pending state; beyond that (qLogEI only, up to 63 - the same limit ``_check_batch_size`` admits for recommend()) the
         columns come from ``cross_cov_many`` and the joint kernel takes the pending statistics explicitly, as in the greedy loop."""
         beta = getattr(acqf, "beta", 0.2)
+        prog = self._program
+        okw = {} if prog is None else {"objective": prog}
         if len(pend) == 0:
             z = sobol_normal_base_samples(acqf.n_mc_samples, 1, seed)[:, 0]
-            return eng.mc_acq(acqf.kind, mean, var, z, self._best_f, sign, beta)
+            return eng.mc_acq(acqf.kind, mean, var, z, self._best_f, sign, beta, **okw)
         z = sobol_normal_base_samples(acqf.n_mc_samples, 1 + len(pend), seed)
         if len(pend) > _lib.MAX_PENDING:
+            if prog is not None:
+                raise IncompatibilityError(
+                    f"{len(pend)} pending / batch rows exceed the largest joint q-batch of the HIP kernels for a transformed target "
+                    f"({_lib.MAX_PENDING + 1} points).")
             if acqf.kind != "qLogEI" or len(pend) > _lib.MAX_PENDING_BIG:
                 raise IncompatibilityError(
                     f"{len(pend)} pending / batch rows exceed the largest joint q-batch of the HIP kernels for '{type(acqf).__name__}' "
@@ -635,9 +666,11 @@ class HipRecommenderImpl:
             cross = eng.cross_cov_many(comp, pend)
             s = eng.qlogei_pending_big(mean, var, cross, pend, z, self._best_f, sign)
         else:
-            eng.set_pending(pend)
+            stats = eng.set_pending(pend)
             cross = eng.cross_cov(comp)
-            s = eng.mc_acq(acqf.kind, mean, var, z, self._best_f, sign, beta, cross=cross)
+            if prog is not None:
+                okw["stats"] = stats
+            s = eng.mc_acq(acqf.kind, mean, var, z, self._best_f, sign, beta, cross=cross, **okw)
         eng.set_pending(None)
         return s
 
@@ -653,10 +686,10 @@ class HipRecommenderImpl:
         eng = surrogate.engine
         mean, var = eng.posterior(comp)
         if acqf.is_analytic:
-            s = self._analytic_scores(eng, acqf, mean, var, surrogate.sign)
+            s = self._analytic_scores(eng, acqf, mean, var, self._sign(surrogate))
             return pd.Series(s.cpu().numpy(), index=candidates.index)
         pend = self._pending_comp if self._pending_comp is not None else np.zeros((0, comp.shape[1]))
-        s = self._mc_scores_with_pending(eng, acqf, comp, mean, var, pend, self._sampler_seed(), surrogate.sign)
+        s = self._mc_scores_with_pending(eng, acqf, comp, mean, var, pend, self._sampler_seed(), self._sign(surrogate))
         return pd.Series(s.cpu().numpy(), index=candidates.index)
 
     def joint_acquisition_value(self, candidates: pd.DataFrame, searchspace, objective, measurements,
@@ -705,6 +738,7 @@ def recommender_fields(with_base_fields: bool = True, surrogate_factory=HipGauss
         "_cand_cache": field(default=None, init=False, eq=False, repr=False),
         "_nehvi": field(default=None, init=False, eq=False, repr=False),
         "_acqf_in_use": field(default=None, init=False, eq=False, repr=False),
+        "_program": field(default=None, init=False, eq=False, repr=False),  # ObjectiveProgram of a transformed single target
     }
     if with_base_fields:
         f["acquisition_function"] = field(default=None, converter=convert_acqf, kw_only=True)

@@ -269,6 +269,41 @@ int bbh_qlogei_pending_big(bbh_handle* h, const double* mean_dev, const double* 
                            int64_t N, int64_t p, const double* mean_p_host, const double* cov_pp_host,
                            const double* z_host, int64_t S, double best_f, double sign, const uint8_t* alive_dev,
                            double* scores_dev);
+/* ---- target transformations as MC objectives ------------------------------------------------------------------------------
+ * The reference fits the surrogate on the raw target and applies the target's transformation per posterior sample, in front of
+ * the acquisition utility (baybe/acquisition/_builder.py:211-254, baybe/objectives/base.py:130-150,
+ * baybe/transformations/basic.py); a minimised target appends a negation (objectives/base.py:100-105).  An objective program is
+ * that transformation as at most 8 scalar operations, applied first to last to every sample y: */
+enum bbh_objective_op {
+  BBH_OBJ_AFFINE = 0,   /* p0 y + p1 */
+  BBH_OBJ_CLAMP = 1,    /* min(max(y, p0), p1); -inf / +inf = no bound */
+  BBH_OBJ_TWOSIDED = 2, /* y < p2 ? (y - p2) p0 : (y - p2) p1 */
+  BBH_OBJ_BELL = 3,     /* exp(-((y - p0) / p1)^2 / 2) */
+  BBH_OBJ_LOG = 4,
+  BBH_OBJ_EXP = 5,
+  BBH_OBJ_POW = 6,      /* y^p0, p0 integer-valued */
+  BBH_OBJ_SIGMOID = 7   /* 1 / (1 + exp(p1 (y - p0))) */
+};
+#define BBH_OBJ_MAX_OPS 8
+typedef struct bbh_objective_prog {
+  int32_t n_ops;
+  int32_t op[BBH_OBJ_MAX_OPS];
+  double p[BBH_OBJ_MAX_OPS][3];
+} bbh_objective_prog;
+/* bbh_mc_acq_q1 with g = prog(mu + sd z_s) in place of sign (mu + sd z_s): replaces the reference's
+ * acqf(objective=GenericMCObjective(transformation))(X) for t-batches of one point.  kind: BBH_ACQ_QLOGEI ... BBH_ACQ_QPSTD;
+ * qUCB / qPSTD use the mean of g over the samples (BoTorch's obj.mean(dim=0)). */
+int bbh_mc_acq_obj_q1(bbh_handle* h, int32_t kind, const bbh_objective_prog* prog, const double* mean_dev, const double* var_dev,
+                      int64_t N, const double* z_host, int64_t S, double best_f, double beta, const uint8_t* alive_dev,
+                      double* scores_dev);
+/* ... and for the t-batches [x_i ; pending], 1 <= p <= 15, with the pending statistics given by the caller as for
+ * bbh_qlogei_pending_big (the same call of the reference with X_pending set): per sample the maximum over the 1 + p points of the
+ * utility of prog(y_r), for qLogEI the fat maximum.  NaN for a row whose joint covariance does not factor at any jitter level,
+ * -inf for a masked row. */
+int bbh_mc_acq_obj_pending(bbh_handle* h, int32_t kind, const bbh_objective_prog* prog, const double* mean_dev,
+                           const double* var_dev, const double* cross_dev, int64_t N, int64_t p, const double* mean_p_host,
+                           const double* cov_pp_host, const double* z_host, int64_t S, double best_f, double beta,
+                           const uint8_t* alive_dev, double* scores_dev);
 /* Analytic family (q = 1): PM, PSTD(+-), UCB(beta), EI, LogEI, PI; sigma^2 clamped at 1e-12. */
 int bbh_analytic_acq(bbh_handle* h, int32_t kind, const double* mean_dev, const double* var_dev, int64_t N,
                      double best_f, double sign, double beta, int32_t maximize, const uint8_t* alive_dev,
