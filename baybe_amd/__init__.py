@@ -7,5 +7,17 @@ mirror of BayBE's surrogate / recommender plug-in surface (``surrogates``, ``rec
 
 from baybe_amd._lib import HipError, HipUnavailableError, is_available, library_path
 
-__all__ = ["HipError", "HipUnavailableError", "is_available", "library_path"]
+
+
+def __getattr__(name):
+    """``farthest_point_sampling`` / ``HipFPSRecommender`` (``baybe_amd.sampling``), imported on first use: the module pulls in pandas
+    and attrs, which a plain ``import baybe_amd`` does not need."""
+    if name in ("farthest_point_sampling", "HipFPSRecommender"):
+        from baybe_amd import sampling
+
+        return getattr(sampling, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
+__all__ = ["HipError", "HipUnavailableError", "is_available", "library_path", "farthest_point_sampling", "HipFPSRecommender"]
 __version__ = "0.1.0"

@@ -202,6 +202,12 @@ SIGNATURES = {
     "bbh_content_key": (C.c_uint64, [C.POINTER(C.c_void_p), c_int64_p, C.c_int32, C.c_int32]),
     "bbh_argmax": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, c_double_p, c_int64_p]),
     "bbh_topk": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, c_double_p, c_int64_p]),
+    "bbh_fps_prepare": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, c_double_p, c_double_p, C.c_void_p, C.c_int64,
+                                  C.c_void_p, C.c_int64]),
+    "bbh_fps_farthest_pair": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, c_double_p, c_int64_p,
+                                        c_int64_p]),
+    "bbh_fps_greedy": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, c_int64_p, C.c_int64, C.c_int64,
+                                 C.c_int64, c_int64_p, c_double_p, c_int64_p]),
     "bbh_comm_unique_id": (C.c_int, [C.c_void_p, C.c_int64]),
     "bbh_comm_init": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64]),
     "bbh_comm_destroy": (C.c_int, [C.c_void_p]),

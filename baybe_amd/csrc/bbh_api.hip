@@ -140,6 +140,7 @@ extern "C" int bbh_destroy(bbh_handle* h) {
   bbh_select_destroy(h);
   bbh_nehvi_destroy(h);
   bbh_sobol_destroy(h);
+  bbh_fps_destroy(h);
   bbh_flow_destroy(h);
   bbh_free_model_public(h);
   if (h->d_ws) hipFree(h->d_ws);
@@ -308,6 +309,7 @@ extern "C" int bbh_trim(bbh_handle* h, int64_t keep_bytes) {
   if (!h || keep_bytes < 0) return -1;
   BBH_HIP_TRY(h, hipSetDevice(h->device));
   BBH_HIP_TRY(h, hipStreamSynchronize(h->stream));
+  bbh_fps_reset(h);
   if (h->d_ws && h->ws_bytes > (size_t)keep_bytes) {
     hipFree(h->d_ws);
     h->d_ws = nullptr;

@@ -395,6 +395,7 @@ struct bbh_handle {
   void* nehvi_state = nullptr;    // device-resident box decompositions + their scratch (bbh_nehvi.hip), null until bbh_cells_build_dev
   void* select_state = nullptr;   // chunk keys, result block and base-sample tables of the selection kernels (bbh_select.hip)
   void* sobol_state = nullptr;    // staging of the device-side base-sample draw (bbh_sobol.hip), null until bbh_sobol_normal_dev
+  void* fps_state = nullptr;      // keys, minimum distances and result blocks of farthest point sampling (bbh_fps.hip)
   // timing
   int timing = 0;  // 0 off, 1 every kernel family, otherwise 2 x (bit mask of the families that record events)
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -496,6 +497,8 @@ int bbh_upload_z(bbh_handle* h, const double* z_host, size_t count);  // host do
 void bbh_select_destroy(bbh_handle* h);  // bbh_select.hip
 void bbh_nehvi_destroy(bbh_handle* h);   // bbh_nehvi.hip
 void bbh_sobol_destroy(bbh_handle* h);   // bbh_sobol.hip
+void bbh_fps_destroy(bbh_handle* h);     // bbh_fps.hip
+void bbh_fps_reset(bbh_handle* h);       // bbh_fps.hip: ends the selection in progress (it points into caller-owned memory)
 void bbh_flow_destroy(bbh_handle* h);    // bbh_fitflow.hip
 bool bbh_fit_flow_launch(bbh_handle* h, const double* theta_dev, double* out_dev, int* info_dev, bool tail_only, const double* theta_host = nullptr,
                          bool split = false, int skip_mt = 0, bool prepare_only = false);  // split: two launches - the factorisation with K^-1's tiles, then everything behind them; skip_mt: tail form without the M-tile roles

@@ -968,6 +968,44 @@ class HipGP:
         )
         return vals, idx
 
+    # ---- farthest point sampling (baybe_amd.sampling) ------------------------------------------------------------
+    def fps_prepare(self, X, mean: np.ndarray, scale: np.ndarray, order=None):
+        """``P [d, ldp]`` (device, fp64): the rows ``order`` of ``X [N, d]`` (device tensor; ``None``: all rows in place) as
+        ``(X - mean) / scale``, transposed (``bbh_fps_prepare``; asynchronous).  ``ldp`` = the row count padded to 256."""
+        torch = self._torch()
+        N, d = X.shape
+        M = N if order is None else int(order.shape[0])
+        ldp = -(-M // 256) * 256
+        P = torch.empty((d, ldp), dtype=torch.float64, device=X.device)
+        mean = np.ascontiguousarray(mean, dtype=np.float64)
+        scale = np.ascontiguousarray(scale, dtype=np.float64)
+        self._check(self._lib.bbh_fps_prepare(self._h, X.data_ptr(), N, d, X.stride(0), _dp(mean), _dp(scale),
+                                              None if order is None else order.data_ptr(), M, P.data_ptr(), ldp), "bbh_fps_prepare")
+        return P
+
+    def fps_farthest_pair(self, P, M: int, alive=None):
+        """(d^2, a, b): the live ranks a < b of ``P [d, ldp]`` (first ``M`` columns) with the largest squared distance; bit-equal
+        maxima resolve to the smallest a, then the smallest b (``bbh_fps_farthest_pair``)."""
+        v, a, b = C.c_double(), C.c_int64(), C.c_int64()
+        self._check(self._lib.bbh_fps_farthest_pair(self._h, P.data_ptr(), M, P.shape[0], P.stride(0),
+                                                    None if alive is None else alive.data_ptr(), C.byref(v), C.byref(a), C.byref(b)),
+                    "bbh_fps_farthest_pair")
+        return v.value, a.value, b.value
+
+    def fps_greedy(self, P, M: int, alive=None, starts=None, n_picks: int = 0, k: int = -1, want_count: bool = False):
+        """(ranks, d2, count) of ``bbh_fps_greedy``: ``starts`` (ranks) begins a selection on ``P``, ``None`` continues the handle's;
+        ``k < 0`` takes the last of the tied rows at each of ``n_picks`` picks, ``k >= 0`` the k-th at one pick; ``count`` (with
+        ``want_count``) is the number of tied rows the next pick would choose from."""
+        ranks = np.empty(max(n_picks, 1), dtype=np.int64)
+        d2 = np.empty(max(n_picks, 1))
+        count = C.c_int64(-1)
+        st = None if starts is None else np.ascontiguousarray(starts, dtype=np.int64)
+        self._check(self._lib.bbh_fps_greedy(
+            self._h, P.data_ptr(), M, P.shape[0], P.stride(0), None if alive is None else alive.data_ptr(),
+            None if st is None else st.ctypes.data_as(_lib.c_int64_p), 0 if st is None else len(st), n_picks, k,
+            ranks.ctypes.data_as(_lib.c_int64_p), _dp(d2), C.byref(count) if want_count else None), "bbh_fps_greedy")
+        return ranks[:n_picks], d2[:n_picks], count.value
+
     # ---- row-sharded selection through the library's own RCCL communicator ---------------------------------
     def comm_unique_id(self) -> bytes:
         buf = C.create_string_buffer(256)

@@ -6,9 +6,11 @@ try:  # pragma: no cover - baybe is not importable in the build container
     from baybe.exceptions import (  # type: ignore
         IncompatibilityError,
         IncompatibleAcquisitionFunctionError,
+        IncompatibleArgumentError,
         IncompatibleSurrogateError,
         ModelNotTrainedError,
         NotEnoughPointsLeftError,
+        UnusedObjectWarning,
     )
 except Exception:  # noqa: BLE001
 
@@ -20,6 +22,12 @@ except Exception:  # noqa: BLE001
 
     class IncompatibleAcquisitionFunctionError(IncompatibilityError):
         """An incompatible acquisition function was selected."""
+
+    class IncompatibleArgumentError(IncompatibilityError):
+        """An incompatible argument was passed to a callable."""
+
+    class UnusedObjectWarning(UserWarning):
+        """A method or function was called with undesired arguments which indicates an unintended user fault."""
 
     class NotEnoughPointsLeftError(Exception):
         """More recommendations are requested than there are viable candidates left."""

@@ -24,6 +24,7 @@ from __future__ import annotations
 import attrs
 
 from baybe_amd.recommenders import HipRecommenderImpl, recommender_fields
+from baybe_amd.sampling import HipFPSRecommenderImpl, fps_recommender_fields
 from baybe_amd.surrogates import HipCompositeImpl, HipGPSurrogateImpl, composite_fields, gp_surrogate_fields
 
 
@@ -61,3 +62,25 @@ def make_baybe_classes(surrogate_base=None, recommender_base=None, discrete_comp
     for cls in (surrogate, composite, recommender):
         cls.__module__ = __name__
     return surrogate, composite, recommender
+
+
+def make_baybe_fps_recommender(base=None, discrete_compatibility=None):
+    """``HipFPSRecommender`` as a subclass of BayBE's ``NonPredictiveRecommender``
+    (``baybe/recommenders/pure/nonpredictive/base.py:17-58``): the counterpart of BayBE's ``FPSRecommender`` for the first,
+    model-free batch of a campaign, e.g. ``TwoPhaseMetaRecommender(initial_recommender=HipFPSRecommender(),
+    recommender=HipBotorchRecommender())``.  The base's ``recommend`` (refusal of pending experiments, warnings about unused
+    measurements / objective, candidate extraction) stays in charge and calls the overridden ``_recommend_discrete``.
+
+    Without arguments the base is imported from ``baybe``; the parameters exist so that the layout can be tested against a replica."""
+    if base is None:
+        from baybe.recommenders.pure.nonpredictive.base import NonPredictiveRecommender as base
+    if discrete_compatibility is None:
+        from baybe.searchspace.core import SearchSpaceType
+
+        discrete_compatibility = SearchSpaceType.DISCRETE
+    recommender = attrs.make_class("HipFPSRecommender", fps_recommender_fields(), bases=(HipFPSRecommenderImpl, base), slots=False)
+    recommender.__doc__ = ("Initial recommender selecting candidates by farthest point sampling on an MI355X "
+                           "(``baybe.recommenders.pure.nonpredictive.base.NonPredictiveRecommender``).")
+    recommender.compatibility = discrete_compatibility
+    recommender.__module__ = __name__
+    return recommender

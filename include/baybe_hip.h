@@ -462,6 +462,35 @@ int bbh_argmax(bbh_handle* h, const double* scores_dev, int64_t N, double* best_
 int bbh_topk(bbh_handle* h, const double* scores_dev, int64_t N, int64_t k, double* vals_host,
              int64_t* idx_host);
 
+/* ---- farthest point sampling (the initial, non-Bayesian recommendation) --------------------
+ * Replaces baybe/utils/sampling_algorithms.py:15-172 (farthest_point_sampling) as FPSRecommender._recommend_discrete calls it
+ * (baybe/recommenders/pure/nonpredictive/sampling.py:146-177), without the N x N matrix of sklearn.metrics.pairwise_distances
+ * (sampling_algorithms.py:120-126).  Every comparison is decided by  d^2(x, y) = sum_k (x_k - y_k) * (x_k - y_k),  k ascending from
+ * 0.0, each operation rounded to fp64 and nothing contracted; ties are resolved in RANKS, the positions in
+ * np.lexsort(tuple(points.T)) (sampling_algorithms.py:117). */
+/* StandardScaler.transform + the reordering points[sort_idx] (sampling.py:153-161, sampling_algorithms.py:117-118):
+ * P_dev[k * ldp + r] = (X_dev[order_dev[r] * ldx + k] - mean_host[k]) / scale_host[k] for r < M, k < d - IEEE subtraction and
+ * division, bit for bit numpy's (X - mean) / scale - and 0 for M <= r < ldp.  order_dev [M] holds rows of X_dev [N, ldx]
+ * (null: the identity, M <= N).  Asynchronous on the handle's stream. */
+int bbh_fps_prepare(bbh_handle* h, const double* X_dev, int64_t N, int32_t d, int64_t ldx, const double* mean_host,
+                    const double* scale_host, const int64_t* order_dev, int64_t M, double* P_dev, int64_t ldp);
+/* np.argmax(dist_matrix) of the "farthest" initialisation (sampling_algorithms.py:131-135): the pair of live ranks a < b with the
+ * largest d^2; bit-equal maxima resolve to the smallest a, then the smallest b.  P_dev [d, ldp] as bbh_fps_prepare leaves it,
+ * alive_dev [M] uint8 or null (all rows live); 2 <= M < 2^31 - 256, M <= 65535 * 256, d <= 768.  a = b = -1 with fewer than two
+ * live rows.  Synchronises the stream. */
+int bbh_fps_farthest_pair(bbh_handle* h, const double* P_dev, int64_t M, int32_t d, int64_t ldp, const uint8_t* alive_dev,
+                          double* d2_host, int64_t* a_host, int64_t* b_host);
+/* The selection loop (sampling_algorithms.py:144-169).  n_start > 0 begins a selection from start_ranks_host [n_start] (the
+ * initial selection, in ranks) on P_dev / alive_dev, which must stay valid while the selection continues; n_start = 0 continues
+ * the handle's selection (the matrix arguments are ignored).  Then n_picks picks: each takes, among the live unselected rows whose
+ * minimum d^2 to the selection is the maximum, the k-th in rank order - k < 0: the last one (max_indices[-1], random_tie_break
+ * off), any number of picks enqueued back to back with one synchronisation; k >= 0 (np.random.choice over the tied rows, drawn
+ * by the caller): n_picks <= 1.  ranks_host / d2_host [n_picks]: the picked ranks and the minimum d^2 each was picked at.
+ * count_host (may be null): the number of tied rows the NEXT pick would choose from. */
+int bbh_fps_greedy(bbh_handle* h, const double* P_dev, int64_t M, int32_t d, int64_t ldp, const uint8_t* alive_dev,
+                   const int64_t* start_ranks_host, int64_t n_start, int64_t n_picks, int64_t k, int64_t* ranks_host,
+                   double* d2_host, int64_t* count_host);
+
 /* The joint q'-batch and qLogNEHVI kernels split the MC samples into slices when a candidate set alone would not fill the chip; the
  * slice count - and with it the order in which a candidate's partial sums are added - follows the number of candidate rows.
  * rows > 0 fixes the row count the heuristic sees (a row shard passes the GLOBAL count: every rank then adds in the order the
