@@ -684,6 +684,7 @@ class HipGP:
             raise ModelFittingError(str(ex)) from ex
         self.params = params
         self.jitter = jit.value
+        self._p, self._pend_stats = 0, None  # (bbh_factorize drops the pending points of the previous factorisation)
 
     # ---- posterior ------------------------------------------------------------------------
     def _as_dev(self, X):
@@ -872,7 +873,7 @@ class HipGP:
         """Pending points = base pending + greedy picks (candidate first, then pending)."""
         if X_pending is None or len(X_pending) == 0:
             self._check(self._lib.bbh_pending_set(self._h, None, 0, None, None), "bbh_pending_set")
-            self._pend_stats = None
+            self._p, self._pend_stats = 0, None
             return None, None
         P = np.ascontiguousarray(X_pending, dtype=np.float64)
         p = P.shape[0]
@@ -889,7 +890,8 @@ class HipGP:
         torch = self._torch()
         X = self._as_dev(X)
         N = X.shape[0]
-        cross = torch.empty((N, self._p), dtype=torch.float64, device=X.device)
+        # (no pending points - never set, cleared, or dropped by a new factorisation: the library's own error, not an AttributeError)
+        cross = torch.empty((N, getattr(self, "_p", 0)), dtype=torch.float64, device=X.device)
         self._check(self._lib.bbh_cross_cov(self._h, X.data_ptr(), N, X.stride(0), cross.data_ptr()), "bbh_cross_cov")
         return cross
 

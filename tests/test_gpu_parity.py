@@ -623,6 +623,9 @@ def test_composite_kernels_data_term_posterior_and_greedy(gp, name, tl):
     for i in (0, 17, 599):
         _, cov = om.posterior_joint(np.vstack([cand[i:i + 1], P]))
         assert np.allclose(cr[i], cov[0, 1:], rtol=1e-7, atol=1e-12), (i, cr[i], cov[0, 1:])
+    from _pending_cases import batched_cross  # every row (the batched form is pinned to posterior_joint in test_pending_cases_cpu.py)
+
+    assert np.allclose(cr, batched_cross(om, cand[:600], P), rtol=1e-7, atol=1e-12)
     os.environ["BBH_COOPG_CROSS"] = "0"
     try:
         g2 = engine.HipGP(0)
@@ -1016,6 +1019,9 @@ def test_linear_polynomial_and_periodic_kernels(gp, which):
     for i in (0, 151, 299):
         _, cov = om.posterior_joint(np.vstack([cand[i:i + 1], P]))
         assert np.allclose(cr[i], cov[0, 1:], rtol=1e-7, atol=1e-11), (i, cr[i], cov[0, 1:])
+    from _pending_cases import batched_cross  # every row (the batched form is pinned to posterior_joint in test_pending_cases_cpu.py)
+
+    assert np.allclose(cr, batched_cross(om, cand[:300], P), rtol=1e-7, atol=1e-11)
 
 
 def test_joint_batches_beyond_sixteen_points(gp):
