@@ -217,6 +217,7 @@ SIGNATURES = {
         [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, c_double_p, c_int64_p, c_double_p],
     ),
     "bbh_last_posterior_form": (C.c_int, [C.c_void_p]),
+    "bbh_last_posterior_seeded": (C.c_int, [C.c_void_p]),
     "bbh_last_nei_form": (C.c_int, [C.c_void_p]),
     "bbh_last_fit_form": (C.c_int, [C.c_void_p]),
     "bbh_timing_enable": (C.c_int, [C.c_void_p, C.c_int]),

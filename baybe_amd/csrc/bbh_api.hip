@@ -33,6 +33,7 @@ static bbh_switches bbh_read_switches() {
       {"BBH_KV_LDS", INT, 0, nullptr, &S::kv_lds_blocks},
       {"BBH_COOP", INT, 0, nullptr, &S::coop_mode},
       {"BBH_COOP_SMALL", NOT, '0', &S::coop_small, nullptr},
+      {"BBH_COOP_SEED", NOT, '0', &S::coop_seed, nullptr},
       {"BBH_COOPG_CROSS", NOT, '0', &S::coopg_cross_on, nullptr},
       {"BBH_SMALL", NOT, '0', &S::small_on, nullptr},
       {"BBH_SMALL_FORCE", IS, '1', &S::small_force, nullptr},
@@ -326,6 +327,7 @@ extern "C" int bbh_trim(bbh_handle* h, int64_t keep_bytes) {
 
 // ---- instrumentation ------------------------------------------------------------------------
 extern "C" int bbh_last_posterior_form(bbh_handle* h) { return h ? h->last_form : -1; }
+extern "C" int bbh_last_posterior_seeded(bbh_handle* h) { return h ? (h->last_form == 1 && h->last_seeded) : -1; }
 extern "C" int bbh_last_fit_form(bbh_handle* h) { return h ? h->last_fit_form : -1; }
 
 extern "C" int bbh_timing_enable(bbh_handle* h, int enable) {

@@ -201,6 +201,7 @@ struct bbh_switches {
   int kv_global_mode = -1;        // BBH_KV_GLOBAL: 0 never use global slabs, 1 always, unset: by size
   int kv_lds_blocks = -1;         // BBH_KV_LDS: cap on LDS-cached k-blocks per wave (-1 = as many as fit)
   int coop_mode = 1;              // BBH_COOP: 0 never use the cooperative form, 1 where it pays (default), 2 wherever instantiated
+  bool coop_seed = true;          // BBH_COOP_SEED=0: the augmented distance GEMM in the cooperative form everywhere (A/B)
   bool coop_small = true;         // BBH_COOP_SMALL=0: the eight-round cooperative instantiation for small models too (A/B)
   bool coopg_cross_on = true;     // BBH_COOPG_CROSS=0: composite models' mean-only / cross passes through the materialised path (A/B)
   bool small_on = true;           // BBH_SMALL=0: keep the cooperative form for n <= 64 (A/B)
@@ -344,6 +345,10 @@ struct bbh_handle {
   double* d_rstream = nullptr;    // [4 waves][rstream_frags][64]
   int64_t rstream_frags = 0;
   int coop_g0 = 0;
+  int coop_kds = 0;               // k-steps of the seeded distance GEMM of the cooperative form; 0: the augmented stream is used
+  double* d_trainfrag_s = nullptr;  // [nb][coop_kds][64] training fragments without augmentation rows, scaled by sqrt(5) | [16 nb] squared norms
+  int64_t tf_s_elems = 0;
+  int last_seeded = 0;            // the last cooperative launch (last_form == 1) was the seeded one: bbh_last_posterior_seeded
   int last_form = -1;             // bbh_last_posterior_form
   int last_fit_form = -1;         // bbh_last_fit_form (enum bbh_fit_form)
   int last_nei_form = -1;         // bbh_last_nei_form: 1 fused (bbh_score_nei), 2 unfused (bbh_nei_q1)

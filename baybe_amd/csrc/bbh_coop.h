@@ -87,6 +87,8 @@ struct CoopArgs {
   const double* rstream;  // [4 waves][frags][64] operand slices
   int64_t frags;          // fragments per wave
   int g0;                 // first group that exists: 8 - nb / 4
+  // seeded distance GEMM (KVF bit 8): f.trainfrag is the stream without the two augmentation rows, scaled by sqrt(5), and
+  const double* na = nullptr;  // [16 nb] the training rows' squared norms in the same coordinates (padding rows: far-away marker)
 };
 
 // fragments of the groups before G (in the full 8-round numbering)
@@ -97,10 +99,14 @@ __host__ __device__ constexpr int coop_frags_before(int G) { return 16 * (G * BB
 // (2 x 64 registers: 256 VGPRs in all, no spills).  Measured: not faster than NT = 1 (4.72 vs 4.68 ms) - see bbh_panel.hip.
 // OPEN: the operand slice continues behind this group with at least BBH_COOP_PAIRS more fragment pairs whatever the model
 // size (the two-sweep form, bbh_coop2.h): the ring is always refilled and the waits never shorten.
+// KVF bit 8 (SEED): the distance GEMM starts from seed = |a|^2 + |b|^2 (kvp_dist_seeded); na_next: the squared norms of k-block
+// tbn's training rows in LDS, addressed as alpha_next (a read on lgkmcnt: the counted vmcnt waits of the ring are untouched).
 template <int G, int KD, int KVF, bool PRODUCE, int NT, bool OPEN = false>
 __device__ __forceinline__ void coop_group(const WaveCtx (&c)[NT], const double* rs, const double* tfn, const bbh_lds_double* kv_cur,
                                            bbh_lds_double* kv_mine_next, const bbh_lds_double* alpha_next, int tbn, int cw,
-                                           d4 (&acc)[NT][BBH_COOP_ROUNDS], d2 (&ring)[BBH_COOP_PAIRS], double (&accm)[NT]) {
+                                           d4 (&acc)[NT][BBH_COOP_ROUNDS], d2 (&ring)[BBH_COOP_PAIRS], double (&accm)[NT],
+                                           const bbh_lds_double* na_next = (const bbh_lds_double*)nullptr) {
+  constexpr bool SEED = (KVF & 8) != 0;
   // rs: this wave's operand slice at the start of the group (wave-uniform); tfn: training fragments of k-block tbn
   // (wave-uniform); the lane's slot inside a fragment (pair) is added by the load.  kv_cur / kv_mine_next: tile 0's
   // buffers, tile t's follow at t * BBH_COOP_KV_TILE doubles.
@@ -115,7 +121,11 @@ __device__ __forceinline__ void coop_group(const WaveCtx (&c)[NT], const double*
   double tfv[KD];
   d4 dsa[NT], dsb[NT];
   KvState<BBH_KV_NU> P;
-  double kv[NT][4], kvx[NT][4], kvn[NT][4], alv[4];
+  double kv[NT][4], kvx[NT][4], kvn[NT][4], alv[4], nav[4];
+  if constexpr (PRODUCE && SEED) {
+#pragma unroll
+    for (int r = 0; r < 4; r++) nav[r] = na_next[4 * r];
+  }
   if constexpr (PRODUCE) {
     static_for<0, KD>([&](auto kc) __attribute__((always_inline)) {
       constexpr int k = decltype(kc)::value;
@@ -188,7 +198,12 @@ __device__ __forceinline__ void coop_group(const WaveCtx (&c)[NT], const double*
         if constexpr (!BBH_COOP_ABLATE_KV) {
           static_for<0, NT>([&](auto tc_) __attribute__((always_inline)) {
             constexpr int t = decltype(tc_)::value;
-            kvp_dist<KD>(c[t], tfv, dsa[t], dsb[t]);
+            if constexpr (SEED) {
+              const d4 seed = {nav[0] + c[t].nbn, nav[1] + c[t].nbn, nav[2] + c[t].nbn, nav[3] + c[t].nbn};
+              kvp_dist_seeded<KD>(c[t], tfv, seed, dsa[t], dsb[t]);
+            } else {
+              kvp_dist<KD>(c[t], tfv, dsa[t], dsb[t]);
+            }
           });
         }
       }
@@ -215,15 +230,19 @@ __device__ __forceinline__ void coop_group(const WaveCtx (&c)[NT], const double*
 // GMIN: the first round that can exist.  GMIN = 4 (n <= 256) instantiates only rounds 4 .. 7: four accumulator blocks instead of
 // eight, 115 - 123 VGPRs instead of 153 - 193, i.e. four workgroups per CU instead of two or three - the small models BayBE
 // campaigns live in have little MFMA work per tile to hide the per-tile set-up and the kernel-value chains behind.  GMIN = 6
-// (n <= 128): two accumulator blocks, <= 102 VGPRs, five workgroups per CU.
+// (n <= 128): two accumulator blocks, <= 102 VGPRs, five workgroups per CU - only for the k-step counts that fit that cap without a
+// spill (bbh_fused_coop_s.hip: a spilled register may be one an inline-assembly load is still writing).
 template <int KD, int KVF, int NT, int GMIN = 0>
 __global__ __launch_bounds__(256, (GMIN >= 6 ? 5 : GMIN >= 4 ? 4 : BBH_COOP_WAVES)) void bbh_coop_posterior_kernel(const CoopArgs ca) {
   const FusedArgs& a = ca.f;
-  extern __shared__ __attribute__((aligned(16))) double s_mem[];  // alpha [16 nb] | kv [NT][2][4][256] | red [NT][2][4][16]
+  extern __shared__ __attribute__((aligned(16))) double s_mem[];  // alpha [16 nb] | (SEED) na [16 nb] | kv [NT][2][4][256] | red [NT][2][4][16]
+  constexpr bool SEED = (KVF & 8) != 0;
+  static_assert(!SEED || (KVF & 6) == 0, "the seeded stream carries the Matern-5/2 constant");
   const int l = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int cnd = l & 15, q = l >> 4;
   double* s_alpha = s_mem;
-  double* s_kv = s_alpha + 16 * a.nb;
+  double* s_na = s_alpha + 16 * a.nb;
+  double* s_kv = s_na + (SEED ? 16 * a.nb : 0);
   double* s_red = s_kv + NT * BBH_COOP_KV_TILE;
   const int64_t tile0 = (int64_t)blockIdx.x * (16 * NT);
 
@@ -241,6 +260,11 @@ __global__ __launch_bounds__(256, (GMIN >= 6 ? 5 : GMIN >= 4 ? 4 : BBH_COOP_WAVE
   // is 8 us of which the MFMA work is 5)
   double tfv0[KD];
   kvp_load<KD>(a.trainfrag + l, w, tfv0);
+  double na0[4];  // SEED: the squared norms of k-block w's rows, from memory (the LDS copy is not complete before the first barrier)
+  if constexpr (SEED) {
+#pragma unroll
+    for (int r = 0; r < 4; r++) na0[r] = ca.na[16 * w + 4 * r + q];
+  }
 #pragma unroll
   for (int t = 0; t < NT; t++) {
     const int64_t row = (tile0 + 16 * t + cnd < a.N) ? tile0 + 16 * t + cnd : a.N - 1;
@@ -264,6 +288,8 @@ __global__ __launch_bounds__(256, (GMIN >= 6 ? 5 : GMIN >= 4 ? 4 : BBH_COOP_WAVE
   // alpha -> LDS: requested after the candidate-row loads, so that its round trip passes under theirs
   if (!(BBH_COOP_ABLATE_PRO & 1))
     for (int s = threadIdx.x; s < 16 * a.nb; s += 256) s_alpha[s] = a.meanB[(int64_t)s * 16];
+  if constexpr (SEED)
+    for (int s = threadIdx.x; s < 16 * a.nb; s += 256) s_na[s] = ca.na[s];
 #pragma unroll
   for (int t = 0; t < NT; t++) {
     double nbsum = 0.0;
@@ -273,17 +299,21 @@ __global__ __launch_bounds__(256, (GMIN >= 6 ? 5 : GMIN >= 4 ? 4 : BBH_COOP_WAVE
       double v = 0.0;
       if (dim < a.dn) {
         v = (BBH_COOP_ABLATE_PRO & 2) ? 0.01 * (double)(dim + cnd) : fma(xval[t][k], xscl[k], xofs[k]);
+        if constexpr (SEED) v *= BBH_SQRT5;  // as the training side (host_pack_trainfrag_seeded): sqrt(5) times the scaled coordinate
         nbsum = fma(v, v, nbsum);
       }
       c[t].cf[k] = v;
     }
     nbsum += __shfl_xor(nbsum, 16, 64);
     nbsum += __shfl_xor(nbsum, 32, 64);
+    if constexpr (!SEED) {
 #pragma unroll
-    for (int k = 0; k < KD; k++) {
-      if (4 * k + q == a.dn) c[t].cf[k] = 1.0;
-      if (4 * k + q == a.dn + 1) c[t].cf[k] = nbsum;
+      for (int k = 0; k < KD; k++) {
+        if (4 * k + q == a.dn) c[t].cf[k] = 1.0;
+        if (4 * k + q == a.dn + 1) c[t].cf[k] = nbsum;
+      }
     }
+    c[t].nbn = nbsum;
     int tc = 0;
     if constexpr ((KVF & 1) != 0) {  // task / outputscale table: the candidate's own task selects the table row
       if (a.task_col >= 0) {
@@ -313,6 +343,7 @@ __global__ __launch_bounds__(256, (GMIN >= 6 ? 5 : GMIN >= 4 ? 4 : BBH_COOP_WAVE
 
   bbh_lds_double* kvb = (bbh_lds_double*)(s_kv + l);  // [tile][buffer][k-block of the group][4 values x 64 lanes]
   const bbh_lds_double* alq = (const bbh_lds_double*)(s_alpha + q);  // alpha[16 tb + 4 r + q]
+  const bbh_lds_double* naq = (const bbh_lds_double*)(s_na + q);     // (SEED) |a|^2 of the same rows
   const int g0 = ca.g0;
   double accm[NT];
   d4 acc[NT][BBH_COOP_ROUNDS];
@@ -342,7 +373,12 @@ __global__ __launch_bounds__(256, (GMIN >= 6 ? 5 : GMIN >= 4 ? 4 : BBH_COOP_WAVE
 #pragma unroll
       for (int t = 0; t < NT; t++) {
         d4 dsa, dsb;
-        kvp_dist<KD>(c[t], tfv, dsa, dsb);
+        if constexpr (SEED) {
+          const d4 seed = {na0[0] + c[t].nbn, na0[1] + c[t].nbn, na0[2] + c[t].nbn, na0[3] + c[t].nbn};
+          kvp_dist_seeded<KD>(c[t], tfv, seed, dsa, dsb);
+        } else {
+          kvp_dist<KD>(c[t], tfv, dsa, dsb);
+        }
         kv_all<KVF>(c[t], w, dsa, dsb, kv0[t]);
       }
     }
@@ -364,7 +400,7 @@ __global__ __launch_bounds__(256, (GMIN >= 6 ? 5 : GMIN >= 4 ? 4 : BBH_COOP_WAVE
       const int tbn = 4 * (G + 1 - g0) + w;  // real k-block this wave produces for the next group
       constexpr bool PRODUCE = G + 1 < BBH_COOP_ROUNDS;
       coop_group<G, KD, KVF, PRODUCE, NT>(c, rs, a.trainfrag + (int64_t)tbn * KD * 64, kvb + (G & 1) * 4 * 256,
-                                          kvb + (((G + 1) & 1) * 4 + w) * 256, alq + 16 * tbn, tbn, cw, acc, ring, accm);
+                                          kvb + (((G + 1) & 1) * 4 + w) * 256, alq + 16 * tbn, tbn, cw, acc, ring, accm, naq + 16 * tbn);
       rs += (int64_t)16 * (BBH_COOP_ROUNDS - G) * 64;
 #if !BBH_COOP_ABLATE_BARRIER  // (timing experiment only: wrong results without the barrier)
       if constexpr (PRODUCE) __syncthreads();
@@ -445,6 +481,10 @@ bool bbh_coop_launch_a(int kd, int kind, bool has_tbl, dim3 grid, size_t lds, hi
 bool bbh_coop_launch_b(int kd, int kind, bool has_tbl, dim3 grid, size_t lds, hipStream_t s, const CoopArgs& a);
 // n <= 256 (g0 >= 4): the four-round instantiations (Matérn-5/2 with and without table; 2, 4, 6, 8 k-steps)
 bool bbh_coop_launch_small(int kd, int kind, bool has_tbl, dim3 grid, size_t lds, hipStream_t s, const CoopArgs& a);
+// Seeded distance GEMM (KVF bit 8; Matérn-5/2 with and without the table): kds = k-steps of the stream without augmentation
+// rows, 2 - 8 and 12 (bbh_fused_coop_c.hip; with small_ok 2 - 6 at n <= 256, 2 and 3 at n <= 128: bbh_fused_coop_s.hip)
+bool bbh_coop_seed_launch(int kds, bool has_tbl, dim3 grid, size_t lds, hipStream_t s, const CoopArgs& a, bool small_ok);
+bool bbh_coop_seed_launch_small(int kds, bool has_tbl, dim3 grid, size_t lds, hipStream_t s, const CoopArgs& a);
 
 #define BBH_COOP_DISPATCH_KD(KDV, NTV)                                                                                        \
   if (kd == KDV) {                                                                                                       \

@@ -75,6 +75,7 @@ struct WaveCtx {
   int nl, ncache;  // k-blocks [0, ncache) are cached at all
   const bbh_lds_double* al;  // alpha in LDS + (lane >> 4), or null: mean through the MFMA form (pending columns)
   int kd, kind, T, tc, q, l, dn;
+  double nbn;     // seeded distance GEMM (bbh_coop.h): the candidate's own squared norm, in the stream's scaled coordinates
   double cf[16];  // BBH_CANDREG: the wave's candidate fragments in registers (pipelined forms, KD <= 16)
 };
 
@@ -295,6 +296,21 @@ __device__ __forceinline__ void kvp_dist(const WaveCtx& c, const double (&tfv)[K
 #endif
 }
 
+// Seeded form (cooperative kernel, BBH_CANDREG without BBH_DIST_ASM): r2 = |a|^2 + |b|^2 - 2 a.b with the rank-2 norm term as
+// the initial value of the first accumulator chain (the C operand of its first MFMA) instead of as two more K columns of the
+// GEMM: KD = ceil(dn / 4) k-steps instead of ceil((dn + 2) / 4).  seed[r] = |a_(4 r + q)|^2 + |b_cnd|^2.
+template <int KD>
+__device__ __forceinline__ void kvp_dist_seeded(const WaveCtx& c, const double (&tfv)[KD], const d4& seed, d4& da, d4& db) {
+  static_assert(BBH_CANDREG && !BBH_DIST_ASM, "the seeded distance GEMM reads the candidate fragments from registers");
+  da = seed;
+  db = (d4){0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+  for (int k = 0; k < KD; k += 2) {
+    da = mfma_f64(tfv[k], c.cf[k], da);
+    if (k + 1 < KD) db = mfma_f64(tfv[k + 1], c.cf[k + 1], db);
+  }
+}
+
 // Kernel values of NU (= 4) scaled squared distances in lockstep, cut into BBH_KV_STEPS micro-steps of NU to
 // 2 NU VALU instructions so that the caller can place them between MFMAs in program order (the compiler's
 // scheduler clumps library sqrt()/exp() calls behind the MFMAs even when asked to interleave them
@@ -304,6 +320,17 @@ __device__ __forceinline__ void kvp_dist(const WaveCtx& c, const double (&tfv)[K
 //         with error O(eps^4) is kept behind BBH_KV_SQRT_NR=0 and measured 1 % slower);
 //   exp:  -s = k ln2 + r, |r| <= ln2/2, degree-11 minimax polynomial (3e-18), scaled with v_ldexp_f64 (huge s, e.g. the
 //         padding marker r2 = 1e8, underflows to 0 there); r2 = 0 is handled by a 1e-300 floor.
+//         k without v_rndne_f64 / v_cvt_i32_f64: u = fma(s, -log2(e), 1.5 * 2^52) is rounded to an integer by the addition
+//         itself, kf = u - 1.5 * 2^52 is k as a double and the low dword of u is k as a 32-bit integer (two's complement).
+//         Valid while s log2(e) < 2^31, i.e. s < 1.48e9, r2 < 4.4e17 (Matern-5/2): the padding marker (r2 = 1e8) and every
+//         r2 <= 1e16 lie inside; the RBF argument is clamped to 800.
+// KVF bit 8 (seeded cooperative form): the operands of the distance GEMM carry the kind's constant (sqrt(5) on both sides), so
+// the GEMM delivers t = 5 r2 directly and the multiplication of micro-step 0 is gone.
+// Per value: 27 VALU instructions (Matern-5/2; 26 in the seeded form), was 28 with v_mul + v_rndne + v_cvt for the split.
+// Beside an MFMA stream v_rndne_f64, v_cvt_i32_f64, v_ldexp_f64 and v_max_f64 all cost what v_fma_f64 costs (6.2 - 6.4 SIMD cycles,
+// v_rsq_f64 18.4, a 32-bit integer add 3.0: scripts/mfma_valu_overlap_probe.hip, profiles/kv_chain_valu_probe.log), so the saving is
+// the count alone, and v_ldexp_f64 stays: two integer instructions and a clamp would cost more.  Per wave and tile of the
+// cooperative kernel (8 productions of 4 values): 1299 VALU + 616 MFMA instructions in the ISA, were 1341 + 624 (KERNELS.md 4.1).
 // Measured against the libm form on 1e6 x 512 values: tests/test_gpu_parity.py::test_pipelined_kernel_matches_plain_form, scripts/gpu_kv_accuracy.py.
 #define BBH_KV_STEPS 18
 #ifndef BBH_KV_SQRT_NR
@@ -331,6 +358,8 @@ template <int KVF, int NU, int step>
 __device__ __forceinline__ void kv_micro(KvState<NU>& P, const WaveCtx& c, int tb, int r0, const d4& da, const d4& db,
                                          double (&out)[4]) {
   constexpr bool HAS_TBL = (KVF & 1) != 0, RBFK = (KVF & 2) != 0;  // table multiply / RBF instead of Matern
+  constexpr bool PRESCALED = (KVF & 8) != 0;  // the distance GEMM delivers t = KC1 r2 (seeded stream: operands scaled by sqrt(KC1))
+  constexpr double RND = 6755399441055744.0;  // 1.5 * 2^52
   constexpr bool M32K = (KVF & 4) != 0;  // Matern-3/2: k = (1 + s) exp(-s), s = sqrt(3 r2)  (5/2: 1 + s + s^2/3, s = sqrt(5 r2))
   constexpr double KC1 = M32K ? 3.0 : 5.0, KC2 = M32K ? 0.0 : 1.0 / 3.0;
   constexpr double LOG2E = 1.4426950408889634074, LN2_HI = 6.93147180369123816490e-01,
@@ -352,7 +381,7 @@ __device__ __forceinline__ void kv_micro(KvState<NU>& P, const WaveCtx& c, int t
         if (RBFK)
           P.g[u] = __builtin_fmin(__builtin_fmax(0.5 * r2, 0.0), 800.0);  // RBF: s = r2 / 2, no sqrt
         else
-          P.t[u] = __builtin_fmax(KC1 * r2, 1e-300);
+          P.t[u] = __builtin_fmax(PRESCALED ? r2 : KC1 * r2, 1e-300);
         if (HAS_TBL) P.te[u] = c.taskext[16 * tb + 4 * (r0 + u) + c.q];
       }
       break;
@@ -411,26 +440,28 @@ __device__ __forceinline__ void kv_micro(KvState<NU>& P, const WaveCtx& c, int t
 #endif
     case 7:
 #pragma unroll
-      BBH_KV_EACH P.kf[u] = __builtin_rint(P.g[u] * -LOG2E);
-      if (!RBFK) {
+      BBH_KV_EACH P.y[u] = fma(P.g[u], -LOG2E, RND);  // y = k + 1.5 * 2^52 from here on (the sqrt residual is dead)
+      if (!RBFK) {  // the whole polynomial factor here and both reduction steps in micro-step 8: g and kf die there, and no
+                    // micro-step boundary carries more live registers than the v_rndne / v_cvt form did (the n <= 128
+                    // instantiations sit at their 96-register cap)
 #pragma unroll
         BBH_KV_EACH P.q[u] = M32K ? 1.0 : fma(P.g[u], KC2, 1.0);
-      }
-      break;
-    case 8:
-#pragma unroll
-      BBH_KV_EACH P.t[u] = fma(P.kf[u], -LN2_HI, -P.g[u]);  // t = reduced argument r from here on
-      if (!RBFK) {
 #pragma unroll
         BBH_KV_EACH P.q[u] = fma(P.q[u], P.g[u], 1.0);
       }
       break;
-    case 9:
+    case 8:
+#pragma unroll
+      BBH_KV_EACH P.kf[u] = P.y[u] - RND;
+#pragma unroll
+      BBH_KV_EACH P.t[u] = fma(P.kf[u], -LN2_HI, -P.g[u]);  // t = reduced argument r from here on
 #pragma unroll
       BBH_KV_EACH P.t[u] = fma(P.kf[u], -LN2_LO, P.t[u]);
+      break;
+    case 9:
 #pragma unroll
       BBH_KV_EACH {
-        P.ki[u] = (int)P.kf[u];
+        P.ki[u] = __double2loint(P.y[u]);  // no instruction: the low register of the pair
         if (HAS_TBL) P.tv[u] = c.tbl[c.tc * c.T + P.te[u]];
       }
       break;

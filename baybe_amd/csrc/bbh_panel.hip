@@ -189,6 +189,52 @@ static void host_pack_trainfrag(const bbh_handle* h, const double* pts, int64_t 
     }
 }
 
+// Training fragments of the seeded distance GEMM (cooperative form, bbh_coop.h) for blocks [0, nb): the layout of
+// host_pack_trainfrag with kds = ceil(dn / 4) (rounded up to an instantiated count) k-steps and no augmentation rows,
+//   frag[tb][k][l] = -2 A[16 tb + (l & 15)][4 k + (l >> 4)],  A = sqrt(5) (x - centre) / lengthscale,
+// followed by na[16 nb] = |A_i|^2 (what the kernel seeds the accumulator with).  The Matérn-5/2 constant is folded into the
+// coordinates - the candidate side multiplies its scaled coordinate by the same sqrt(5) - so the GEMM delivers t = 5 r2.
+// Padding rows: zero fragments and the far-away marker of the augmented stream in these coordinates (5e8: the value underflows to 0).
+static void host_pack_trainfrag_seeded(const bbh_handle* h, const double* pts, int64_t cnt, int64_t nb, int kds, std::vector<double>& out) {
+  const int dn = h->dn;
+  const double* ls = h->theta.data() + 3;
+  out.assign((size_t)nb * kds * 64 + (size_t)16 * nb, 0.0);
+  double* na = out.data() + (size_t)nb * kds * 64;
+  std::vector<double> a(dn);
+  for (int64_t tb = 0; tb < nb; tb++)
+    for (int c16 = 0; c16 < 16; c16++) {
+      const int64_t i = tb * 16 + c16;
+      if (i >= cnt) {
+        na[i] = 5e8;
+        continue;
+      }
+      double sum = 0.0;
+      for (int j = 0; j < dn; j++) {
+        a[j] = BBH_SQRT5 * ((pts[i * dn + j] - h->xcenter[j]) / ls[j]);
+        sum += a[j] * a[j];
+      }
+      na[i] = sum;
+      for (int dim = 0; dim < dn; dim++) out[((size_t)tb * kds + dim / 4) * 64 + (dim % 4) * 16 + c16] = -2.0 * a[dim];
+    }
+}
+
+// k-steps of the seeded distance GEMM for this model, 0 where it saves nothing over the augmented stream's h->kd (or BBH_COOP_SEED=0,
+// or no instantiation: Matérn-5/2 only).  n <= 256 (g0 >= 4): a small-model instantiation of the augmented stream is kept where
+// the seeded stream has only the eight-round one (fewer workgroups per CU cost more than the k-steps save).
+static int bbh_coop_seed_kds(const bbh_handle* h, bool has_tbl, int g0) {
+  if (!h->sw.coop_seed || h->desc.kernel_kind != BBH_KERNEL_MATERN52) return 0;
+  int kds = (h->dn + 3) / 4;
+  kds = kds <= 8 ? (kds < 2 ? 2 : kds) : 12;
+  if (kds >= h->kd || 4 * kds < h->dn) return 0;
+  CoopArgs ask{};
+  ask.g0 = g0;
+  if (g0 >= 4 && h->sw.coop_small) {
+    if (bbh_coop_seed_launch_small(kds, has_tbl, dim3(0), 0, nullptr, ask)) return kds;
+    if (bbh_coop_launch_small(h->kd, h->desc.kernel_kind, has_tbl, dim3(0), 0, nullptr, ask)) return 0;
+  }
+  return bbh_coop_seed_launch(kds, has_tbl, dim3(0), 0, nullptr, ask, false) ? kds : 0;
+}
+
 // Models the generic-production cooperative kernel covers: everything bbh_materialised_only() sends to the materialised-K*
 // path whose factors are Matérn-5/2, -3/2, RBF, rational quadratic or piecewise polynomial with q >= 1 (Matérn-1/2 and the
 // q = 0 piecewise polynomial (1 - r)^j are not smooth at r = 0: the |a|^2 + |b|^2 - 2ab distances lose sqrt(eps) there, so they
@@ -381,6 +427,20 @@ int bbh_pack_operands(bbh_handle* h) {
                          h->d_rstream);
       h->coop_g0 = g0;
       h->coop_ready = true;
+      // ... and the training fragments of its seeded distance GEMM where that has fewer k-steps
+      h->coop_kds = bbh_coop_seed_kds(h, has_tbl0, g0);
+      if (h->coop_kds) {
+        std::vector<double> tfs;
+        host_pack_trainfrag_seeded(h, h->xn_host.data(), h->n, nb, h->coop_kds, tfs);
+        if (!h->d_trainfrag_s || h->tf_s_elems != (int64_t)tfs.size()) {
+          if (h->d_trainfrag_s) hipFree(h->d_trainfrag_s);
+          h->d_trainfrag_s = nullptr;
+          BBH_HIP_TRY(h, hipMalloc((void**)&h->d_trainfrag_s, sizeof(double) * tfs.size()));
+          h->tf_s_elems = (int64_t)tfs.size();
+        }
+        BBH_HIP_TRY(h, hipMemcpyAsync(h->d_trainfrag_s, tfs.data(), sizeof(double) * tfs.size(), hipMemcpyHostToDevice, s));
+        BBH_HIP_TRY(h, hipStreamSynchronize(s));  // (pageable staging vector)
+      }
     }
   }
   // ---- generic-production cooperative form: the same operand slices, per-factor training fragments and candidate scaling ----
@@ -677,9 +737,21 @@ int bbh_launch_fused(bbh_handle* h, const double* X_dev, int64_t N, int64_t ldx,
     // was built and measured in round 2: 4.72 vs 4.68 ms on the bench shape, profiles/r02_libs_nt2.log.  What the MFMA pipe
     // loses is per candidate, not per operand fragment; the variant was removed from the library, coop_group keeps its NT
     // template parameter.)
-    const size_t clds = sizeof(double) * (16 * (size_t)h->nb + (2 * 4 * 256 + 128));
+    ca.na = nullptr;
     const dim3 cgrid((unsigned)((N + 15) / 16));
-    bbh_coop_launch(kdc, a.kind, has_tbl, cgrid, clds, h->stream, ca, h->sw.coop_small);
+    h->last_seeded = h->coop_kds > 0;
+    if (h->coop_kds) {  // seeded distance GEMM: its own training fragments, the squared norms next to alpha in LDS (+ 4 KB at n = 512)
+      ca.f.trainfrag = h->d_trainfrag_s;
+      ca.na = h->d_trainfrag_s + (size_t)h->nb * h->coop_kds * 64;
+      const size_t clds = sizeof(double) * (32 * (size_t)h->nb + (2 * 4 * 256 + 128));
+      if (!bbh_coop_seed_launch(h->coop_kds, has_tbl, cgrid, clds, h->stream, ca, h->sw.coop_small)) {
+        h->err = "cooperative posterior form: no seeded instantiation for this model although its operands were packed";
+        return -6;
+      }
+    } else {
+      const size_t clds = sizeof(double) * (16 * (size_t)h->nb + (2 * 4 * 256 + 128));
+      bbh_coop_launch(kdc, a.kind, has_tbl, cgrid, clds, h->stream, ca, h->sw.coop_small);
+    }
     h->last_form = 1;
     BBH_HIP_TRY(h, hipGetLastError());
     return 0;

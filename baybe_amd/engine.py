@@ -1055,6 +1055,10 @@ class HipGP:
         return {0: "windowed", 1: "cooperative", 2: "materialised", 3: "cooperative-2sweep", 4: "cooperative-generic",
                 5: "register-resident", 6: "feature-space"}.get(self._lib.bbh_last_posterior_form(self._h), "none")
 
+    def posterior_distance_seeded(self) -> bool:
+        """Whether the last variance pass ran the cooperative form with the seeded distance GEMM (``BBH_COOP_SEED=0``: never)."""
+        return self._lib.bbh_last_posterior_seeded(self._h) == 1
+
     def fit_evaluation_form(self) -> str:
         """Which path the last fit evaluation (``data_term``, every objective call of ``fit``) ran as - after a give-up of a dataflow
         launch, the path that produced the returned numbers (``enum bbh_fit_form`` in include/baybe_hip.h)."""

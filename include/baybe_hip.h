@@ -540,6 +540,9 @@ int bbh_timing_read(bbh_handle* h, double* fused_ms_total, int64_t* fused_launch
  * Polynomial, Periodic: bbh_coopg_posterior_kernel), 5 = register- / LDS-resident (n <= 128, bbh_small_posterior_kernel),
  * 6 = feature space (BBH_KERNEL_RFF: bbh_rff_posterior_kernel), -1 = none yet. */
 int bbh_last_posterior_form(bbh_handle* h);
+/* 1 if the last variance pass ran the cooperative form with the seeded distance GEMM (the squared norms as the accumulator's
+ * initial value, ceil(d / 4) k-steps), 0 if it ran any other form (BBH_COOP_SEED=0 keeps the augmented stream everywhere). */
+int bbh_last_posterior_seeded(bbh_handle* h);
 /* Form the last qNEI / qLogNEI scoring pass of this handle ran as: 1 = fused (bbh_score_nei), 2 = unfused (bbh_nei_q1),
  * -1 = none yet. */
 int bbh_last_nei_form(bbh_handle* h);
