@@ -208,6 +208,11 @@ SIGNATURES = {
                                         c_int64_p]),
     "bbh_fps_greedy": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, c_int64_p, C.c_int64, C.c_int64,
                                  C.c_int64, c_int64_p, c_double_p, c_int64_p]),
+    "bbh_pam_dist_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
+    "bbh_pam_assign": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "bbh_pam_cost": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                               C.c_int64, C.c_void_p]),
+    "bbh_pam_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "bbh_comm_unique_id": (C.c_int, [C.c_void_p, C.c_int64]),
     "bbh_comm_init": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64]),
     "bbh_comm_destroy": (C.c_int, [C.c_void_p]),

@@ -1,0 +1,316 @@
+"""k-medoids clustering on the device, and the initial recommender built on it.
+
+``k_medoids`` mirrors the reference's own ``KMedoids`` with ``method="alternate"``
+(``baybe/utils/clustering_algorithms/third_party/kmedoids.py``: same validation and error texts, same warnings, the same draws from the
+same generator) and ``HipPAMRecommenderImpl._recommend_discrete`` mirrors ``SKLearnClusteringRecommender._recommend_discrete`` with
+``PAMClusteringRecommender``'s selection (``baybe/recommenders/pure/nonpredictive/clustering.py:100-132, 174-193``), without the N x N
+distance matrix the reference builds on the host (``kmedoids.py:231``: 80 GB at 1e5 candidates).  The kernels are in
+``csrc/bbh_pam.hip``.
+
+The contract (``tests/_oracle_pam.py`` restates it in numpy, from these words):
+
+Positions are the rows of the point matrix in the order given - the reference does not sort here, so there are no ranks - and every
+tie goes to the first in position / cluster order, which is what numpy's ``argmin`` gives the reference on equal values.
+
+Arithmetic.  ``d2(x, y) = sum_k (x_k - y_k) * (x_k - y_k)``, k ascending from 0.0, nothing contracted; ``dist = sqrt(d2)``, IEEE,
+correctly rounded (bit-equal to ``np.sqrt``); distances, not squares, are compared and summed; every sum that decides something is
+sequential in ascending position (``np.cumsum(v)[-1]``).
+
+Generator.  ``random_state=None``: ``np.random.mtrand._rand`` (what ``check_random_state(None)`` returns); an int: ``RandomState(int)``;
+an instance: itself.
+
+``init="k-medoids++"`` (``kmedoids.py:438-511``).  ``T = 2 + int(np.log(k))``; ``c0 = rs.randint(N)``; ``closest = dist(c0, .) *
+dist(c0, .)`` (the reference squares the stored distance); ``pot = seqsum(closest)``; for each further centre ``rv =
+rs.random_sample(T) * pot``, ``cand = np.searchsorted(np.cumsum(closest), rv)``, and the trials run in order: ``new = minimum(closest,
+dist(cand_t, .)^2)``, kept if it is the first trial or ``seqsum(new) < best_pot`` strictly.  ``init="random"``: ``rs.choice(N, k,
+replace=False)``.
+
+Iteration (``kmedoids.py:254-292``), at most ``max_iter`` times.  ``label[j]``: the smallest cluster index among bit-equal minima of
+``dist(medoid_c, j)``.  For every cluster, from the labels of this iteration: an empty cluster warns in the reference's words and is
+skipped; ``cost[i] = sum over the members j, ascending, of dist(i, j)`` for each member i; the new medoid is the smallest position
+among bit-equal minima, adopted only if ``min_cost < curr_cost`` strictly, where ``curr_cost`` is the medoid's cost - or the first
+member's if the medoid is not a member of its own cluster (duplicate rows; ``np.argmax(cluster_k_idxs == medoid)`` yields 0).  Stop
+when no medoid changed; a last permitted iteration that still changed one warns with the reference's ``ConvergenceWarning`` text.
+
+Result.  Medoid positions in cluster order; final labels, assigned once more from the final medoids; ``inertia = np.sum`` of the
+distance-to-assigned-medoid vector on the host; ``n_iter``, the reference's ``n_iter_``: the index of the last iteration run (0 for
+``max_iter = 0``).
+
+On points in generic position this reproduces the reference's ``medoid_indices_``; where costs are mathematically tied (grids,
+duplicates, two-member clusters) the reference's choice follows the rounding of sklearn's ``|x|^2 + |y|^2 - 2 x.y`` matrix and the rule
+above decides instead.
+"""
+
+from __future__ import annotations
+
+import warnings
+from typing import ClassVar
+
+import attrs
+import numpy as np
+import pandas as pd
+from attrs import field
+from attrs.validators import instance_of
+
+from baybe_amd.sampling import HipFPSRecommenderImpl, _StandAloneFPS, standard_scaling
+
+try:  # the reference warns with sklearn's class; a filter on it must catch ours too
+    from sklearn.exceptions import ConvergenceWarning
+except ImportError:  # pragma: no cover
+
+    class ConvergenceWarning(UserWarning):
+        """Stand-in for ``sklearn.exceptions.ConvergenceWarning`` where sklearn is not installed."""
+
+
+_INIT_METHODS = ["random", "heuristic", "k-medoids++", "build"]
+_MAX_D = 768
+_MAX_ROWS = 2**31 - 256
+
+
+class DeviceRows:
+    """A point matrix resident on the device (``X [n, d]`` as uploaded, with the scaling that turns it into points) and the dense
+    matrix ``P [d, ldp]`` of the rows currently selected, on a model-less ``HipGP`` handle.  This is the whole device surface of the
+    module: the tests double it on the CPU."""
+
+    def __init__(self, values: np.ndarray, mean: np.ndarray, scale: np.ndarray, device: int = 0):
+        from baybe_amd.engine import HipGP
+
+        self.gp = HipGP(device)
+        self.n, self.d = values.shape
+        self.mean, self.scale = mean, scale
+        self.X = self._upload(values)
+        self.select(None)
+
+    def _upload(self, values: np.ndarray):
+        import torch
+
+        return torch.from_numpy(np.ascontiguousarray(values, dtype=np.float64)).to(self.gp._dev())
+
+    def select(self, rows=None):
+        """The points of the calls that follow: the rows ``rows`` of the matrix, in that order (``None``: all of them)."""
+        import torch
+
+        order = None if rows is None else torch.from_numpy(np.ascontiguousarray(rows, dtype=np.int64)).to(self.X.device)
+        self.m = self.n if rows is None else len(rows)
+        self.P = self.gp.fps_prepare(self.X, self.mean, self.scale, order)
+        self._cost = self._perm = None
+
+    def _index(self, idx):
+        import torch
+
+        return torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int64)).to(self.P.device)
+
+    def dist_rows(self, rows) -> np.ndarray:
+        """[T, m]: the distances from the positions ``rows`` to every position."""
+        return self.gp.pam_dist_rows(self.P, self.m, self._index(rows)).cpu().numpy()
+
+    def assign(self, medoids):
+        """(labels int32 [m], dist [m]) on the host."""
+        labels, dist = self.gp.pam_assign(self.P, self.m, self._index(medoids))
+        return labels.cpu().numpy(), dist.cpu().numpy()
+
+    def step(self, medoids):
+        """One iteration: (medoids after the update, indices of the empty clusters, whether a medoid changed).  Labels, the stable
+        grouping, the cost pass and the update are enqueued back to back; reading the medoids and flags is the one synchronisation."""
+        import torch
+
+        k, m = len(medoids), self.m
+        med = self._index(medoids)
+        labels, _ = self.gp.pam_assign(self.P, m, med)
+        grouped, perm = torch.sort(labels, stable=True)  # grouped by label, position order kept inside a cluster
+        # the clusters' column ranges [k + 1], without a read-back (bincount would take one for its bin count)
+        starts = torch.searchsorted(grouped, torch.arange(k + 1, dtype=torch.int32, device=labels.device))
+        zero = torch.zeros(1, dtype=torch.int64, device=labels.device)
+        tile_starts = torch.cat([zero, torch.cumsum((starts[1:] - starts[:-1] + 255) // 256, 0)])
+        Ps = self.P.index_select(1, perm)
+        cost = self.gp.pam_cost(Ps, m, starts, tile_starts, k)
+        flags = self.gp.pam_update(cost, perm, m, starts, med)
+        self._cost, self._perm = cost, perm
+        out = torch.cat([med, flags.to(torch.int64)]).cpu().numpy()
+        f = out[k:]
+        return out[:k].copy(), np.flatnonzero(f == 1).tolist(), bool((f == 2).any())
+
+    def costs(self) -> np.ndarray:
+        """The in-cluster cost of every position as the last ``step`` computed it (before its update)."""
+        import torch
+
+        cost = torch.empty_like(self._cost)
+        cost[self._perm] = self._cost
+        return cost.cpu().numpy()
+
+
+_rows_factory = DeviceRows
+
+
+def _random_state(seed):
+    """``sklearn.utils.check_random_state``."""
+    if seed is None or seed is np.random:
+        return np.random.mtrand._rand
+    if isinstance(seed, (int, np.integer)) and not isinstance(seed, bool):
+        return np.random.RandomState(seed)
+    if isinstance(seed, np.random.RandomState):
+        return seed
+    raise ValueError(f"{seed!r} cannot be used to seed a numpy.random.RandomState instance")
+
+
+def _check_nonnegative_int(value, desc, strict=True):
+    negative = (value is None) or (value <= 0 if strict else value < 0)
+    if negative or not isinstance(value, (int, np.integer)):
+        raise ValueError(f"{desc} should be a nonnegative integer. {value} was given")
+
+
+def _validate(n_clusters, max_iter, init, method, metric):
+    """``KMedoids._check_init_args`` in its order and words (kmedoids.py:168-203), then what the HIP path leaves out."""
+    _check_nonnegative_int(n_clusters, "n_clusters")
+    _check_nonnegative_int(max_iter, "max_iter", False)
+    if not (hasattr(init, "__array__") or (isinstance(init, str) and init in _INIT_METHODS)):
+        raise ValueError("init needs to be one of " + "the following: " + "%s" % (_INIT_METHODS + ["array-like"]))
+    if hasattr(init, "__array__"):
+        raise ValueError("An array-like init is not available on the HIP path; use 'k-medoids++' or 'random'.")
+    if init in ("heuristic", "build"):
+        raise ValueError(f"init='{init}' is not available on the HIP path (its argpartition / BUILD orders on tied sums are not a "
+                         f"contract); use 'k-medoids++' or 'random'.")
+    if method == "pam":
+        raise ValueError("method='pam' is not available on the HIP path; use 'alternate'.")
+    if method != "alternate":
+        raise ValueError(f"method={method} is not supported. Supported methods are 'pam' and 'alternate'.")
+    if metric != "euclidean":
+        raise ValueError(f"metric='{metric}' is not available on the HIP path; only 'euclidean' is.")
+
+
+def _kpp_init(dev, k: int, rs) -> np.ndarray:
+    """``KMedoids._kpp_init`` (kmedoids.py:438-511) on rows of the distance matrix computed on demand."""
+    n = dev.m
+    centers = np.empty(k, dtype=np.int64)
+    trials = 2 + int(np.log(k))
+    centers[0] = rs.randint(n)
+    row = dev.dist_rows(centers[:1])[0]
+    closest = row * row
+    pot = np.cumsum(closest)[-1]
+    for c in range(1, k):
+        rand_vals = rs.random_sample(trials) * pot
+        cand = np.searchsorted(np.cumsum(closest), rand_vals)
+        np.clip(cand, None, n - 1, out=cand)
+        rows = dev.dist_rows(cand)
+        best = best_pot = best_closest = None
+        for t in range(trials):
+            new = np.minimum(closest, rows[t] * rows[t])
+            new_pot = np.cumsum(new)[-1]
+            if best is None or new_pot < best_pot:
+                best, best_pot, best_closest = cand[t], new_pot, new
+        centers[c], pot, closest = best, best_pot, best_closest
+    return centers
+
+
+def _cluster(dev, n_clusters: int, max_iter: int = 100, init="k-medoids++", random_state=None, method="alternate", metric="euclidean"):
+    """``KMedoids(...).fit`` on the selected rows of ``dev``: (medoids, labels, inertia, n_iter)."""
+    rs = _random_state(random_state)
+    _validate(n_clusters, max_iter, init, method, metric)
+    if n_clusters > dev.m:
+        raise ValueError("The number of medoids (%d) must be less than the number of samples %d." % (n_clusters, dev.m))
+    if init == "random":
+        medoids = np.asarray(rs.choice(dev.m, n_clusters, replace=False), dtype=np.int64)
+    else:
+        medoids = _kpp_init(dev, n_clusters, rs)
+    n_iter = 0
+    for n_iter in range(max_iter):
+        medoids, empty, changed = dev.step(medoids)
+        for c in empty:
+            warnings.warn("Cluster {k} is empty! self.labels_[self.medoid_indices_[{k}]] may not be labeled with its corresponding "
+                          "cluster ({k}).".format(k=c))
+        if not changed:
+            break
+        elif n_iter == max_iter - 1:
+            warnings.warn("Maximum number of iteration reached before convergence. Consider increasing max_iter to improve the fit.",
+                          ConvergenceWarning)
+    labels, dist = dev.assign(medoids)
+    return medoids, labels, float(np.sum(dist)), n_iter
+
+
+def k_medoids(points: np.ndarray, n_clusters: int, max_iter: int = 100, init="k-medoids++", random_state=None, *, device: int = 0,
+              return_info: bool = False, method: str = "alternate", metric: str = "euclidean"):
+    """The reference's ``KMedoids(n_clusters, init=init, max_iter=max_iter, random_state=random_state).fit(points)`` on the device: the
+    medoid positions in cluster order (``medoid_indices_``).  With ``return_info`` also ``labels_``, ``inertia_`` and ``n_iter_``."""
+    _validate(n_clusters, max_iter, init, method, metric)  # refused before anything goes to the device
+    values = np.ascontiguousarray(points, dtype=np.float64)
+    if values.ndim != 2 or values.shape[0] < 1 or values.shape[1] < 1:
+        raise ValueError(f"Expected a 2D array with at least one row and one column, got an array of shape {values.shape}.")
+    if values.shape[1] > _MAX_D or values.shape[0] >= _MAX_ROWS:
+        raise ValueError(f"The HIP path takes at most {_MAX_D} columns and fewer than 2^31 - 256 rows, got {values.shape}.")
+    if n_clusters > values.shape[0]:
+        raise ValueError("The number of medoids (%d) must be less than the number of samples %d." % (n_clusters, values.shape[0]))
+    rs = _random_state(random_state)
+    d = values.shape[1]
+    dev = _rows_factory(values, np.zeros(d), np.ones(d), device)  # (x - 0) / 1: the points themselves, bit for bit
+    medoids, labels, inertia, n_iter = _cluster(dev, n_clusters, max_iter, init, rs, method, metric)
+    medoids = [int(i) for i in medoids]
+    return (medoids, labels, inertia, n_iter) if return_info else medoids
+
+
+class HipPAMRecommenderImpl(HipFPSRecommenderImpl):
+    """Behaviour of the k-medoids recommender on an MI355X.  No fields (see ``baybe_amd.plugin``): they are attached by
+    ``attrs.make_class`` - below for the stand-alone class, in ``plugin.make_baybe_pam_recommender`` on top of BayBE's
+    ``NonPredictiveRecommender``, whose ``recommend`` then drives ``_recommend_discrete``.  Copying, pickling and the cache key are
+    the FPS recommender's."""
+
+    __slots__ = ()
+
+    _SHARED_ON_COPY: ClassVar[tuple] = ("_fps_cache",)
+
+    def _resident_rows(self, subspace_discrete):
+        """(rows, labels): the comp rep of the WHOLE discrete subspace with the scaling fitted on it, resident per search-space
+        content and device; later calls send only the candidates' positions."""
+        from baybe_amd.recommenders import _content_hash, _frame_content_hash
+
+        comp_rep = subspace_discrete.comp_rep
+        idx = comp_rep.index
+        idx_key = (idx.start, idx.stop, idx.step) if isinstance(idx, pd.RangeIndex) else _content_hash(np.asarray(idx))
+        key = (comp_rep.shape, tuple(comp_rep.columns), _frame_content_hash(comp_rep), idx_key, self.device)
+        if self._fps_cache is None or self._fps_cache[0] != key:
+            values = np.ascontiguousarray(comp_rep.to_numpy(dtype=np.float64))
+            mean, scale = standard_scaling(values)  # fitted on the entire search space (nonpredictive/clustering.py:107-112)
+            self._fps_cache = (key, _rows_factory(values, mean, scale, self.device), comp_rep.index)
+        return self._fps_cache[1], self._fps_cache[2]
+
+    def _recommend_discrete(self, subspace_discrete, candidates_exp: pd.DataFrame, batch_size: int) -> pd.Index:
+        dev, labels = self._resident_rows(subspace_discrete)
+        pos = None  # the candidates in their own row order (clustering.py:115-116)
+        if len(candidates_exp) != len(labels) or not candidates_exp.index.equals(labels):
+            pos = labels.get_indexer(candidates_exp.index)
+            if (pos < 0).any():
+                raise KeyError("candidates contain rows that are not part of the discrete subspace")
+        dev.select(pos)
+        medoids, _, _, _ = _cluster(dev, batch_size, **self.model_params)
+        return candidates_exp.index[np.asarray(medoids, dtype=np.int64)]
+
+    def __str__(self) -> str:
+        return f"{self.__class__.__name__}(model_params={self.model_params!r})"
+
+
+def _check_model_params(instance, attribute, value):
+    unknown = set(value) - {"max_iter", "init", "random_state", "method", "metric"}
+    if unknown:
+        raise TypeError(f"KMedoids got unexpected model parameters: {sorted(unknown)}")
+
+
+def pam_recommender_fields() -> dict:
+    """attrs fields of the recommender: the reference's one (nonpredictive/clustering.py:159-165) plus the device and the cache."""
+    return {
+        "model_params": field(default=attrs.Factory(lambda: {"max_iter": 100, "init": "k-medoids++"}),
+                              validator=[instance_of(dict), _check_model_params]),
+        "device": field(default=0, validator=instance_of(int), kw_only=True),
+        "_fps_cache": field(default=None, init=False, eq=False, repr=False),
+    }
+
+
+class _StandAlonePAM(HipPAMRecommenderImpl, _StandAloneFPS):
+    """``recommend`` of the stand-alone FPS recommender (the refusals and warnings of ``NonPredictiveRecommender.recommend`` /
+    ``PureRecommender.recommend``) over the k-medoids ``_recommend_discrete``."""
+
+    __slots__ = ()
+
+
+HipPAMClusteringRecommender = attrs.make_class("HipPAMClusteringRecommender", pam_recommender_fields(), bases=(_StandAlonePAM,), slots=False)
+HipPAMClusteringRecommender.__doc__ = "Initial recommender selecting the medoids of a k-medoids clustering on an MI355X (stand-alone)."
+HipPAMClusteringRecommender.__module__ = __name__
+HipPAMClusteringRecommender.compatibility = "DISCRETE"

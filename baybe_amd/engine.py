@@ -1008,6 +1008,47 @@ class HipGP:
             ranks.ctypes.data_as(_lib.c_int64_p), _dp(d2), C.byref(count) if want_count else None), "bbh_fps_greedy")
         return ranks[:n_picks], d2[:n_picks], count.value
 
+    # ---- k-medoids (baybe_amd.clustering): stateless, asynchronous, every buffer a device tensor ------------------
+    def pam_dist_rows(self, P, M: int, rows):
+        """``[T, M]`` distances from the positions ``rows`` (int64 device tensor) to every position of ``P [d, ldp]``
+        (``bbh_pam_dist_rows``)."""
+        torch = self._torch()
+        out = torch.empty((int(rows.shape[0]), M), dtype=torch.float64, device=P.device)
+        self._check(self._lib.bbh_pam_dist_rows(self._h, P.data_ptr(), M, P.shape[0], P.stride(0), rows.data_ptr(), int(rows.shape[0]),
+                                                out.data_ptr()), "bbh_pam_dist_rows")
+        return out
+
+    def pam_assign(self, P, M: int, medoids):
+        """(labels int32 [M], dist [M]): the nearest of the ``medoids`` (int64 device tensor), first in cluster order among bit-equal
+        distances, and the distance to it (``bbh_pam_assign``)."""
+        torch = self._torch()
+        labels = torch.empty(M, dtype=torch.int32, device=P.device)
+        dist = torch.empty(M, dtype=torch.float64, device=P.device)
+        self._check(self._lib.bbh_pam_assign(self._h, P.data_ptr(), M, P.shape[0], P.stride(0), medoids.data_ptr(), int(medoids.shape[0]),
+                                             labels.data_ptr(), dist.data_ptr()), "bbh_pam_assign")
+        return labels, dist
+
+    def pam_cost(self, Ps, M: int, starts, tile_starts, k: int):
+        """``cost [M]`` by grouped column: the sequential sum of the distances from each column of ``Ps [d, M]`` (grouped by label) to
+        the columns of its own cluster (``bbh_pam_cost``).  ``starts`` / ``tile_starts``: int64 device tensors [k + 1]."""
+        torch = self._torch()
+        max_tiles = M // 256 + k
+        table = torch.empty(2 * max_tiles, dtype=torch.int32, device=Ps.device)
+        cost = torch.empty(M, dtype=torch.float64, device=Ps.device)
+        self._check(self._lib.bbh_pam_cost(self._h, Ps.data_ptr(), M, Ps.shape[0], Ps.stride(0), starts.data_ptr(), tile_starts.data_ptr(),
+                                           k, table.data_ptr(), max_tiles, cost.data_ptr()), "bbh_pam_cost")
+        return cost
+
+    def pam_update(self, cost, perm, M: int, starts, medoids):
+        """Moves ``medoids`` (int64 device tensor, in place) to the cheapest member of each cluster where that is strictly cheaper;
+        returns the flags [k] (int32 device tensor: 1 = empty cluster, 2 = medoid changed) (``bbh_pam_update``)."""
+        torch = self._torch()
+        k = int(medoids.shape[0])
+        flags = torch.empty(k, dtype=torch.int32, device=cost.device)
+        self._check(self._lib.bbh_pam_update(self._h, cost.data_ptr(), perm.data_ptr(), M, starts.data_ptr(), k, medoids.data_ptr(),
+                                             flags.data_ptr()), "bbh_pam_update")
+        return flags
+
     # ---- row-sharded selection through the library's own RCCL communicator ---------------------------------
     def comm_unique_id(self) -> bytes:
         buf = C.create_string_buffer(256)

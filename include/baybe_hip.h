@@ -491,6 +491,37 @@ int bbh_fps_greedy(bbh_handle* h, const double* P_dev, int64_t M, int32_t d, int
                    const int64_t* start_ranks_host, int64_t n_start, int64_t n_picks, int64_t k, int64_t* ranks_host,
                    double* d2_host, int64_t* count_host);
 
+/* ---- k-medoids, method "alternate" (the clustering choice for the initial, non-Bayesian recommendation) ----
+ * Replaces baybe/utils/clustering_algorithms/third_party/kmedoids.py as PAMClusteringRecommender drives it
+ * (baybe/recommenders/pure/nonpredictive/clustering.py:100-132, 148-193), without the N x N matrix of pairwise_distances
+ * (kmedoids.py:231).  Positions are the columns of P_dev [d, ldp] in the order given (bbh_fps_prepare with order_dev = the
+ * candidates' rows: a dense matrix of live rows, no masks).  d2(x, y) = sum_k (x_k - y_k) * (x_k - y_k), k ascending from 0.0,
+ * nothing contracted; dist = sqrt(d2), IEEE correctly rounded; DISTANCES are compared and summed; every deciding sum is sequential
+ * in ascending position; every tie goes to the first in position / cluster order (numpy's argmin).  Limits of all four:
+ * 1 <= M < 2^31 - 256, 1 <= d <= 768, 1 <= k <= M.  All four are asynchronous on the handle's stream and keep no state. */
+/* D[medoid candidates, :] (kmedoids.py:481, 490): out_dev [T, M] = dist(rows_dev[t], j); a row index outside [0, M) gives a row of
+ * NaN.  rows_dev [T] int64, T >= 1. */
+int bbh_pam_dist_rows(bbh_handle* h, const double* P_dev, int64_t M, int32_t d, int64_t ldp, const int64_t* rows_dev, int64_t T,
+                      double* out_dev);
+/* np.argmin(D[medoid_idxs, :], axis=0) (kmedoids.py:256, 302) and the distance it found: labels_dev [M] int32 = the smallest cluster
+ * index among bit-equal minima of dist(medoids_dev[c], j), dist_dev [M] that distance (the column minimum behind inertia_,
+ * kmedoids.py:304).  medoids_dev [k] int64; the medoids' coordinates pass through LDS in tiles, so any k <= M works. */
+int bbh_pam_assign(bbh_handle* h, const double* P_dev, int64_t M, int32_t d, int64_t ldp, const int64_t* medoids_dev, int64_t k,
+                   int32_t* labels_dev, double* dist_dev);
+/* np.sum(in_cluster_distances, axis=1) of every cluster at once (kmedoids.py:326-329).  Ps_dev [d, lds]: the points GROUPED by
+ * label with a stable sort (position order survives inside a cluster), cluster c in the columns [starts_dev[c], starts_dev[c + 1]);
+ * tile_starts_dev [k + 1]: exclusive prefix sums of ceil(n_c / 256); both int64.  cost_dev [M], by grouped column:
+ * cost[i] = sum over the columns j of i's cluster, ascending, of dist(i, j) - added one by one in that order.  table_dev
+ * [2 * max_tiles] int32 receives the (cluster, row tile) pairs the grid runs over; max_tiles >= M / 256 + k. */
+int bbh_pam_cost(bbh_handle* h, const double* Ps_dev, int64_t M, int32_t d, int64_t lds, const int64_t* starts_dev,
+                 const int64_t* tile_starts_dev, int64_t k, int32_t* table_dev, int64_t max_tiles, double* cost_dev);
+/* The medoid update of every cluster (kmedoids.py:312-339), one workgroup each: the minimum cost at the smallest grouped column,
+ * curr_cost = the cost at the medoid's column, or at the cluster's first column if the medoid is not a member
+ * (np.argmax(cluster_k_idxs == medoid) = 0), adopted only if min_cost < curr_cost.  perm_dev [M] int64: grouped column -> position.
+ * medoids_dev [k] int64 is updated in place; flags_dev [k] int32: 1 = the cluster is empty (skipped), 2 = its medoid changed. */
+int bbh_pam_update(bbh_handle* h, const double* cost_dev, const int64_t* perm_dev, int64_t M, const int64_t* starts_dev, int64_t k,
+                   int64_t* medoids_dev, int32_t* flags_dev);
+
 /* The joint q'-batch and qLogNEHVI kernels split the MC samples into slices when a candidate set alone would not fill the chip; the
  * slice count - and with it the order in which a candidate's partial sums are added - follows the number of candidate rows.
  * rows > 0 fixes the row count the heuristic sees (a row shard passes the GLOBAL count: every rank then adds in the order the
