@@ -26,7 +26,11 @@
 //   dot kinds        a.b (Linear, Polynomial; a = xn / w)   train [a, 0, 0]     candidate [b, 1, |b|^2]  (|b|^2 is k(x, x)'s argument)
 //   periodic         sum_j sin^2(pi (xn_j - xn'_j) / p_j) / l_j = sum_j (1 - cos al_j cos be_j - sin al_j sin be_j) / (2 l_j)
 //                    train [-cos al / 2l, -sin al / 2l, sum_j 1 / 2l_j]         candidate [cos be, sin be, 1]
-// (padding rows of the training fragments carry 1e8 in the slot that meets the candidate's constant 1: metric 1e8 -> value 0)
+// Padding rows - beyond the n training rows in blocks [0, nb), beyond the p pending points in block nb - are recognised by their
+// INDEX (coopg_produce) and contribute exactly 0.  A large metric says nothing: a rational quadratic factor at r^2 = 1e7 and
+// alpha = 0.4 is still 1.4e-3, a Linear / Polynomial factor grows with its dot product.  (The fragments of such rows still carry
+// 1e8 in the slot that meets the candidate's constant 1, so that every factor's value there is finite and what it always was;
+// nothing reads it as a mark any more.)
 struct CoopGFeat {
   double scl, ofs;
   int src, op;
@@ -44,6 +48,7 @@ struct CoopGArgs {
   const CoopGFeat* feat;          // [F][4 KD]
   double prior_k0;                // k(x, x) without the table / outputscale when no factor is a dot kind: prod_f fos_f or sum_f fos_f
   int has_dot;                    // some factor is Linear / Polynomial: k(x, x) is per candidate
+  int n;                          // training rows: rows [n, 16 nb) of the training blocks are padding
 };
 
 // one k-block's kernel values (4 per lane) for all factors, combined
@@ -51,7 +56,8 @@ template <int KD, int F>
 __device__ __forceinline__ void coopg_produce(const CoopGArgs& g, const WaveCtx& c, const double (&cf)[F][KD], int tb,
                                               double (&out)[4]) {
   double uv[4][BBH_MAX_FACTORS];  // [value][factor] os_f k_f
-  bool pad[4] = {false, false, false, false};
+  // value r of this lane belongs to row 16 tb + 4 r + q: a training row below n, a pending point (block nb) below 16 nb + p
+  const int real_end = (tb < g.c.f.nb) ? g.n : 16 * g.c.f.nb + g.c.f.p;  // wave-uniform
 #pragma unroll
   for (int f = 0; f < F; f++) {
     double tfv[KD];
@@ -89,14 +95,12 @@ __device__ __forceinline__ void coopg_produce(const CoopGArgs& g, const WaveCtx&
       }
     }
 #pragma unroll
-    for (int r = 0; r < 4; r++) {
-      if (f == 0) pad[r] = (da[r] + db[r]) > 1e7;  // padding rows carry |a|^2 = 1e8: exactly 0 for every kernel kind
-      uv[r][f] = g.fos[f] * kv[r];
-    }
+    for (int r = 0; r < 4; r++) uv[r][f] = g.fos[f] * kv[r];
   }
 #pragma unroll
   for (int r = 0; r < 4; r++) {
-    double v = pad[r] ? 0.0 : (F > 1 ? bbh_combine(F, g.combine, g.grp, uv[r]) : uv[r][0]);
+    const bool pad = 16 * tb + 4 * r + c.q >= real_end;
+    double v = pad ? 0.0 : (F > 1 ? bbh_combine(F, g.combine, g.grp, uv[r]) : uv[r][0]);
     if (g.has_tbl) v *= c.tbl[c.tc * c.T + c.taskext[16 * tb + 4 * r + c.q]];
     out[r] = v;
   }

@@ -674,6 +674,7 @@ int bbh_launch_fused(bbh_handle* h, const double* X_dev, int64_t N, int64_t ldx,
     g.has_tbl = has_tbl ? 1 : 0;
     g.jb = ks.jb;
     g.has_dot = 0;
+    g.n = (int)h->n;
     for (int f = 0; f < BBH_MAX_FACTORS; f++) {
       g.kind[f] = ks.kind[f < ks.F ? f : 0];
       g.grp[f] = ks.grp[f];

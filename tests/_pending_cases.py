@@ -62,7 +62,7 @@ LD = np.longdouble
 
 KD_DIMS = {2: 3, 4: 9, 6: 20, 8: 28, 12: 40, 16: 62}
 GENERIC = ("product", "scaled_sum", "three", "sum3", "nested4", "product4", "rq", "piecewise2", "linear", "poly2", "periodic",
-           "product_m12")
+           "product_m12", "matern_x_poly2", "linear_plus_rbf", "nested_dot", "rq_first3", "rq_second")
 
 
 @dataclass(frozen=True)
@@ -74,11 +74,17 @@ class PendModel:
     scale: bool = False    # ScaleKernel around a single kernel (a table without tasks)
     layout: str = "unit"   # "unit": columns in [0, 1], task column last; "mixed": non-unit lo / hi, task column in the middle
     seed: int = 0
+    noise: float = 0.0         # > 0: the noise variance instead of ``fixed_theta``'s e^-5 (RFF: 0.05)
+    ls_scale: float = 1.0      # multiplies the lengthscales of every distance factor (Matérn, RBF, RQ)
+    rq_ls_scale: float = 1.0   # ... and those of the RQ factors alone
+    rq_alpha: float = 0.0      # > 0: alpha of the RQ factors instead of 0.8
 
     @property
     def id(self):
         return (f"{self.kernel}-d{self.d}-n{self.n}" + (f"-T{self.tasks}" if self.tasks else "") + ("-scale" if self.scale else "")
-                + ("-mixed" if self.layout == "mixed" else "") + (f"-s{self.seed}" if self.seed else ""))
+                + ("-mixed" if self.layout == "mixed" else "") + (f"-s{self.seed}" if self.seed else "")
+                + (f"-nz{self.noise:g}" if self.noise else "") + (f"-ls{self.ls_scale:.3g}" if self.ls_scale != 1.0 else "")
+                + (f"-rqls{self.rq_ls_scale:.3g}" if self.rq_ls_scale != 1.0 else "") + (f"-a{self.rq_alpha:g}" if self.rq_alpha else ""))
 
     @property
     def generic(self):
@@ -203,6 +209,14 @@ def _generic_kernel(name):
         "poly2": ScaleKernel(PolynomialKernel(2)),
         "periodic": ScaleKernel(PeriodicKernel()),
         "product_m12": ProductKernel([MaternKernel(0.5), ScaleKernel(RBFKernel())]),  # a Matérn-1/2 factor: materialised K* only
+        # dot kinds inside a composition (a per-candidate k(x, x)), the grouped combine with a dot kind and a periodic factor, RQ as
+        # the first and as a later factor (tests/_generic_variance_cases.py)
+        "matern_x_poly2": ProductKernel([MaternKernel(2.5), ScaleKernel(PolynomialKernel(2))]),
+        "linear_plus_rbf": AdditiveKernel([ScaleKernel(LinearKernel()), ScaleKernel(RBFKernel())]),
+        "nested_dot": AdditiveKernel([ProductKernel([MaternKernel(2.5), LinearKernel()]),
+                                      AdditiveKernel([ScaleKernel(RBFKernel()), ScaleKernel(PeriodicKernel())])]),
+        "rq_first3": ProductKernel([RQKernel(), MaternKernel(2.5), ScaleKernel(RBFKernel())]),
+        "rq_second": ProductKernel([MaternKernel(2.5), ScaleKernel(RQKernel())]),
     }[name]
 
 
@@ -245,17 +259,22 @@ def _make_params(model: PendModel, spec, rng):
             return 1.5 * jit()
         if kind.startswith("piecewise"):
             return 4.0 * math.sqrt(d) * jit()
-        return ls0 * (math.sqrt(F) if F > 1 and spec.combine == "product" else 1.0) * jit()
+        out = ls0 * (math.sqrt(F) if F > 1 and spec.combine == "product" else 1.0) * jit()
+        if model.ls_scale != 1.0:
+            out = out * model.ls_scale
+        if kind == "rq" and model.rq_ls_scale != 1.0:
+            out = out * model.rq_ls_scale
+        return out
 
     p.lengthscale = ls_of(kinds[0])
     if F > 1:
         p.factor_ls = [ls_of(k) for k in kinds[1:]]
         p.factor_os = np.where(np.array([f.scaled for f in spec.factors]), 0.6 + 0.8 * rng.random(F), 1.0)
     if spec.has_rq:
-        p.alpha = np.array([0.8 if k == "rq" else (1.5 if k.startswith("poly") else 1.0) for k in kinds])
+        p.alpha = np.array([(model.rq_alpha or 0.8) if k == "rq" else (1.5 if k.startswith("poly") else 1.0) for k in kinds])
     if spec.has_periodic:
         p.period = [(1.3 * jit()) if k == "periodic" else np.ones(d) for k in kinds]
-    p.noise, p.mean = (0.05 if model.rff else nz), 0.03  # (a rank-2D kernel: at e^-5 the oracle's own mean is 2e-13 from its restatement)
+    p.noise, p.mean = model.noise or (0.05 if model.rff else nz), 0.03  # (a rank-2D kernel: at e^-5 the oracle's own mean is 2e-13 from its restatement)
     if spec.use_outputscale:  # (a Polynomial kernel is (d / 3 + offset)^2 at a typical row: scaled back to the order of 1)
         p.outputscale = 1.7 / (d / 3.0 + 1.5) ** 2 if model.kernel == "poly2" else 1.7
     if model.tasks:
@@ -402,10 +421,15 @@ def batched_cross(om, cand, P):
 
 @functools.lru_cache(maxsize=None)
 def _reference(model: PendModel, p: int, N: int, pend_seed: int) -> Reference:
+    return reference_of(model, _build_case(model, p, N, pend_seed))
+
+
+def reference_of(model: PendModel, d: CaseData) -> Reference:
+    """The oracle's posterior of the rows ``d.cand`` and their cross-covariances with the pending points ``d.P``."""
     from oracle import gp_oracle as go
 
     om = model.build().om
-    d = _build_case(model, p, N, pend_seed)
+    p, N = len(d.P), len(d.cand)
     mean, var = om.posterior(d.cand)
     kxx = go.prior_var(om.spec, om.params, go.normalize_inputs(om.spec, d.cand))
     if p:
@@ -644,14 +668,21 @@ D_COOPG = (("rq", 5, 0), ("piecewise2", 9, 0), ("linear", 20, 0), ("poly2", 5, 0
            ("three", 5, 0), ("sum3", 9, 0), ("three", 20, 0), ("sum3", 28, 0),
            ("nested4", 5, 0), ("product4", 9, 0), ("nested4", 20, 0), ("nested4", 28, 0))
 D_COOPG_FKD = {"rq": 1, "piecewise2": 1, "linear": 1, "poly2": 1, "periodic": 1, "product": 2, "scaled_sum": 2, "three": 3, "sum3": 3,
-               "nested4": 4, "product4": 4}
+               "nested4": 4, "product4": 4, "matern_x_poly2": 2, "linear_plus_rbf": 2, "nested_dot": 4, "rq_first3": 3, "rq_second": 2}
 # materialised K* only: a Matérn-1/2 factor, d = 31 (kd 9 has no instantiation), n = 513 (beyond the cooperative forms)
 D_MATERIALISED = (PendModel("product_m12", 5, 60), PendModel("product", 31, 60), PendModel("product", 5, 513))
 D_RFF = (PendModel("rff16", 5, 60), PendModel("rff64", 5, 60))
 
 
+@functools.lru_cache(maxsize=None)
+def factor_kinds(kernel: str):
+    """The factor kinds of a generic model's built spec (they do not depend on d)."""
+    return tuple(_make_spec(PendModel(kernel, 2, 1), np.zeros(2), np.ones(2)).factor_kinds)
+
+
 def coopg_kd(model: PendModel):
-    feats = max(model.d + 2, 2 * model.d + 1 if model.kernel == "periodic" else 0)
+    """``bbh_coopg_kd``: d + 2 features, 2 d + 1 once ANY factor is periodic; rounded up to an instantiated count, 0: none fits."""
+    feats = max(model.d + 2, 2 * model.d + 1 if "periodic" in factor_kinds(model.kernel) else 0)
     kd = (feats + 3) // 4
     for c in (2, 4, 6, 8):
         if kd <= c:

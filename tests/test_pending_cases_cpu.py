@@ -7,7 +7,7 @@ For every case (one per model, pending set and candidate count):
     rows, in at least three tasks where the model has tasks; p, the number of training blocks and the widths of the variance passes;
 (b) the reference resolves the tolerance: the float64 oracle is within 1e-13 (scaled as the device comparison) of a plain
     ``np.longdouble`` restatement - kernel values, column Cholesky, forward substitution, the same formulas - for cross-covariances,
-    variances and - in the families whose variance pass is compared, C and E - means.  The 1e-11 the device is held to is admissible
+    variances and - in the families whose variance pass is compared, C and E - means (family D's p = 0 pass: a tenth of the tolerance).  The 1e-11 the device is held to is admissible
     against the oracle only under this condition;
 (c) the batched reference is the oracle's joint posterior: ``posterior_joint([x; P])`` row by row on a sample of the rows;
 (d) the case can fail: with columns shifted by one, with column p left at a previous pending point, with the pending tasks taken as
@@ -143,6 +143,11 @@ def test_case_conditions(case):
     # (the mean is compared on the device in the families with a variance pass only: there its own condition holds as well)
     held = [v for k, v in noise.items() if k != "mean" or case.family in "CE"]
     assert max(held) <= pc.REF_NOISE, (case.id, noise)
+    # (family D compares the mean of its p = 0 pass too.  Its models keep ``fixed_theta``'s noise e^-5, where the float64 oracle's mean
+    # of the low-rank kinds - piecewise, Linear, Polynomial - is some 1e-13 from the restatement: held to a tenth of the tolerance,
+    # which leaves the device nine tenths of it; tests/_generic_variance_cases.py has these kinds at noise 0.2 and within 1e-13)
+    if case.family == "D":
+        assert noise["mean"] <= pc.TOL / 10.0, (case.id, noise)
     # (c)
     for i in _rows_sample(N):
         mj, cj = md.om.posterior_joint(np.vstack([d.cand[i:i + 1], d.P]))

@@ -244,11 +244,13 @@ def test_generic_and_other_paths(handles, case):
     Matérn-1/2 factor, d = 31, n = 513) and the feature-space pass of the RFF models, every row of 257 and of 65."""
     g = handles[case.handle]
     d = case.build()
+    ref = case.reference()
     _load(g, case.model)
-    g.posterior(_rows(d.cand))
+    m0, v0 = (_np(t) for t in g.posterior(_rows(d.cand)))
     assert g.posterior_kernel_form() == pc.expected_p0_form(case.model, case.N), (case.id, g.posterior_kernel_form())
-    _, devs = _cross_pass(g, case, case.reference())
+    _, devs = _cross_pass(g, case, ref)
     g.set_pending(None)
+    devs.update({"p0_mean": pc.scaled_mean(m0, ref), "p0_var": pc.scaled_var(v0, ref)})
     _hold(case, devs)
 
 
