@@ -1,4 +1,5 @@
-"""k-medoids clustering on the device, and the initial recommender built on it.
+"""k-medoids and k-means clustering on the device, and the initial recommenders built on them (k-medoids first; the k-means
+contract follows it).
 
 ``k_medoids`` mirrors the reference's own ``KMedoids`` with ``method="alternate"``
 (``baybe/utils/clustering_algorithms/third_party/kmedoids.py``: same validation and error texts, same warnings, the same draws from the
@@ -39,6 +40,49 @@ distance-to-assigned-medoid vector on the host; ``n_iter``, the reference's ``n_
 On points in generic position this reproduces the reference's ``medoid_indices_``; where costs are mathematically tied (grids,
 duplicates, two-member clusters) the reference's choice follows the rounding of sklearn's ``|x|^2 + |y|^2 - 2 x.y`` matrix and the rule
 above decides instead.
+
+
+k-means.  ``k_means`` is the counterpart of ``sklearn.cluster.KMeans(n_clusters, n_init=..., max_iter=..., tol=..., init=...,
+random_state=...).fit`` as the reference's ``KMeansClusteringRecommender`` drives it (``nonpredictive/clustering.py:196-252``, defaults
+``{"max_iter": 1000, "n_init": 50}``), and ``HipKMeansRecommenderImpl._recommend_discrete`` adds that class's selection.  All
+``n_init`` restarts are one device workload (``csrc/bbh_kmeans.hip``): a pass reads each point once per restart TILE, not once per
+restart.  The contract is this project's own arithmetic, not bit-parity with scikit-learn's BLAS form
+(``tests/_oracle_kmeans.py`` restates it in numpy, from these words; device results are held to it within a tolerance, and every
+decision that rests on a comparison is tested where the oracle's own margin is far larger):
+
+Positions and arithmetic.  Points are the rows in the order given.  ``d2(x, c) = sum_k (x_k - c_k)^2`` by direct differences in
+fp64, k ascending; there is no ``|x|^2 + |c|^2 - 2 x.c`` form and no mean-centring (direct differences do not need it).  A label is
+the smallest cluster index among equal minima of ``d2``.
+
+Generator.  The one ``_random_state`` returns.  A restart's draws are ``1 + (k - 1) T`` uniforms with ``T = 2 + int(log k)``,
+whatever the data, so the draws of all ``n_init`` restarts are taken up front, in restart order, as scikit-learn would consume them:
+``rs.random_sample((n_init, 1 + (k - 1) T))``.  First centre: ``choice(N, p=uniform)``, i.e. the row's first uniform searched, side
+right, in ``cumsum(full(N, 1 / N))`` divided by its last entry.  Each further centre: the next ``T`` uniforms times ``pot`` (the sum
+of ``closest``, the ``d2`` of every point to its nearest centre so far) are searched (side left) in the running sum of ``closest``,
+clipped to ``N - 1``; the candidate with the smallest new potential ``sum(minimum(closest, d2(., x_cand)))`` is taken, the first on
+ties.  ``init="random"``: ``rs.choice(N, k, replace=False)`` per restart, in restart order.
+
+Lloyd, at most ``max_iter`` times per restart.  Each iteration computes labels from the current centres, then new centres as member
+sums divided by counts (a cluster whose count is zero after a relocation keeps its sum), and ``shift = sum over centres of
+|new - old|^2``.  Stop if the labels equal the previous iteration's labels (strict); otherwise stop if ``shift <= tol *
+mean(var(points, axis=0))``.  After a non-strict stop - the iteration limit included - labels are assigned once more from the final
+centres.  ``inertia`` is the sum of ``d2`` to the assigned (final) centre; ``n_iter`` is the number of iterations run.
+
+Empty clusters.  The e-th empty cluster, in ascending index, takes the point with the e-th largest ``d2`` to its assigned old
+centre (ties: the smallest position); that point is removed from its old cluster's sum and count, its label stays.  This is
+scikit-learn's relocation, made deterministic.
+
+Restart choice.  The first restart is the best so far; a later one replaces it only if its inertia is strictly smaller AND its
+labels are not the same clustering up to a renaming of the clusters (every label of the later restart meets a single label of the
+best) - scikit-learn's rule.  If the winner has fewer distinct labels than clusters, scikit-learn's ``ConvergenceWarning`` is raised
+in its words.
+
+Selection (``KMeansClusteringRecommender._make_selection_custom``).  Labels are assigned from the final centres of the winner; per
+cluster, in cluster order, the position with the smallest ``sqrt(d2)`` among its own members is taken, the first on ties.  A
+cluster without members yields position 0, as ``argmin`` of an all-infinite column does in the reference.
+
+``max_iter = 0`` is a scikit-learn validation error in ``k_means`` and the recommender; the contract itself (``_kmeans_fit``, the
+oracle) covers it: no iteration, labels from the initial centres, ``n_iter = 0``.
 """
 
 from __future__ import annotations
@@ -137,6 +181,121 @@ class DeviceRows:
         cost = torch.empty_like(self._cost)
         cost[self._perm] = self._cost
         return cost.cpu().numpy()
+
+    # ---- k-means: R restarts side by side.  Centres [R, k, d], labels [R, m] and d2 [R, m] stay on the device. ----
+    def mean_variance(self) -> float:
+        """``mean(var(points, axis=0))``: the scale of the stopping tolerance."""
+        return float(self.P[:, : self.m].var(dim=1, unbiased=False).mean().item())
+
+    def kmeans_seed(self, first, uniforms, k: int) -> np.ndarray:
+        """k-means++ for all restarts at once: the centre positions [R, k], column 0 = ``first``; ``uniforms`` [R, (k - 1) T].
+        ``closest``, the trial potentials, the running sum and the search stay on the device."""
+        import torch
+
+        R = len(first)
+        idx = torch.zeros((R, k), dtype=torch.int64, device=self.P.device)
+        idx[:, 0] = self._index(first)
+        U = None if k == 1 else torch.from_numpy(np.ascontiguousarray(uniforms, dtype=np.float64)).to(self.P.device)
+        self._km_d2 = torch.empty((R, self.m), dtype=torch.float64, device=self.P.device)  # closest now, d2 of the passes later
+        self.gp.kmeans_seed(self.P, self.m, idx, U, 2 + int(np.log(k)), closest=self._km_d2)
+        return idx.cpu().numpy()
+
+    def kmeans_begin(self, idx=None, centres=None):
+        """Starts R restarts from the points at the positions ``idx`` [R, k] (or from ``centres`` [R, k, d]); no labels yet."""
+        import torch
+
+        if centres is None:
+            R, k = idx.shape
+            self._km_C = self.P.index_select(1, self._index(np.reshape(idx, -1))).T.contiguous().reshape(R, k, self.d)
+        else:
+            self._km_C = torch.from_numpy(np.ascontiguousarray(centres, dtype=np.float64)).to(self.P.device)
+            R = self._km_C.shape[0]
+        self._km_labels = torch.full((R, self.m), -1, dtype=torch.int32, device=self.P.device)
+        if getattr(self, "_km_d2", None) is None or tuple(self._km_d2.shape) != (R, self.m):
+            self._km_d2 = torch.empty((R, self.m), dtype=torch.float64, device=self.P.device)
+        self._km_out = None
+        self._km_relocated = np.zeros(R, dtype=bool)
+
+    def _rid(self, restarts):
+        import torch
+
+        return torch.from_numpy(np.ascontiguousarray(restarts, dtype=np.int32)).to(self.P.device)
+
+    def kmeans_step(self, active):
+        """One Lloyd iteration of the restarts ``active``: (labels unchanged [len(active)] bool, shift [len(active)]).  The pass
+        and its finish are enqueued per restart tile; reading the shifts and flags is the one synchronisation.  A restart that met
+        an empty cluster takes the host path for this iteration (``_relocate``)."""
+        import torch
+
+        rid = self._rid(active)
+        out = self._km_out = self.gp.kmeans_pass(self.P, self.m, self._km_C, rid, self._km_labels, self._km_d2, self._km_out)
+        rid = rid.long()
+        host = torch.cat([out["shift"][rid], out["flags"][rid].double()]).cpu().numpy()
+        shift, flags = host[: len(active)].copy(), host[len(active):].astype(np.int64)
+        self._km_relocated[np.asarray(active)] = False
+        for a in np.flatnonzero(flags & 2):
+            shift[a] = self._relocate(int(active[a]))
+        self._km_C[rid] = out["new"][rid]
+        return (flags & 1).astype(bool), shift
+
+    def _relocate(self, r: int) -> float:
+        """The empty clusters of restart ``r`` after its pass, on the host: the e-th of them takes the point with the e-th largest
+        d2 (ties: the smallest position).  Writes the new centres, returns the shift."""
+        import torch
+
+        out = self._km_out
+        labels, d2 = self._km_labels[r].cpu().numpy(), self._km_d2[r].cpu().numpy()
+        sums, counts = out["sums"][r].cpu().numpy(), out["counts"][r].cpu().numpy().astype(np.int64)
+        old = self._km_C[r].cpu().numpy()
+        empty = np.flatnonzero(counts == 0)
+        far = np.lexsort((np.arange(self.m), -d2))[: len(empty)]
+        rows = self.P.index_select(1, self._index(far)).T.cpu().numpy()
+        for e, j, x in zip(empty, far, rows):
+            sums[labels[j]] -= x
+            counts[labels[j]] -= 1
+            sums[e], counts[e] = x, 1
+        new = np.where(counts[:, None] > 0, sums / np.maximum(counts, 1)[:, None], sums)
+        out["new"][r] = torch.from_numpy(new).to(self.P.device)
+        self._km_relocated[r] = True
+        return float(np.sum((new - old) ** 2))
+
+    def kmeans_finish(self, nonstrict) -> np.ndarray:
+        """Assigns the labels of the restarts ``nonstrict`` once more from their final centres; the inertia of every restart [R]."""
+        if len(nonstrict):
+            self._km_out = self.gp.kmeans_pass(self.P, self.m, self._km_C, self._rid(nonstrict), self._km_labels, self._km_d2, self._km_out,
+                                               want_sums=False)
+            self._km_relocated[np.asarray(nonstrict, dtype=np.int64)] = False
+        inertia = self._km_out["inertia"].cpu().numpy().copy()
+        for r in np.flatnonzero(self._km_relocated):  # a strict stop in an iteration that relocated: the centres moved after the pass
+            pts, C, lab = self.P[:, : self.m].T.cpu().numpy(), self._km_C[r].cpu().numpy(), self._km_labels[r].cpu().numpy()
+            acc = np.zeros(self.m)
+            for k in range(self.d):
+                t = pts[:, k] - C[lab, k]
+                acc = acc + t * t
+            inertia[r] = np.sum(acc)
+        return inertia
+
+    def kmeans_labels(self, r: int) -> np.ndarray:
+        return self._km_labels[r].cpu().numpy()
+
+    def kmeans_centres(self, r: int) -> np.ndarray:
+        return self._km_C[r].cpu().numpy()
+
+    def kmeans_sums(self):
+        """(sums [R, k, d], counts [R, k]) of the members as the last ``kmeans_step`` added them (before any relocation)."""
+        return self._km_out["sums"].cpu().numpy(), self._km_out["counts"].cpu().numpy()
+
+    def kmeans_select(self, centres) -> np.ndarray:
+        """The reference's selection from ``centres`` [k, d]: per cluster the member nearest to its centre (a masked argmin on the
+        device, no [N, k] array anywhere); position 0 for a cluster without members."""
+        import torch
+
+        dev = self.P.device
+        C = torch.from_numpy(np.ascontiguousarray(centres, dtype=np.float64)[None]).to(dev)
+        labels = torch.full((1, self.m), -1, dtype=torch.int32, device=dev)
+        d2 = torch.empty((1, self.m), dtype=torch.float64, device=dev)
+        self.gp.kmeans_pass(self.P, self.m, C, torch.zeros(1, dtype=torch.int32, device=dev), labels, d2, None, want_sums=False)
+        return self.gp.kmeans_select(labels[0], d2[0], C.shape[1]).cpu().numpy()
 
 
 _rows_factory = DeviceRows
@@ -314,3 +473,150 @@ HipPAMClusteringRecommender = attrs.make_class("HipPAMClusteringRecommender", pa
 HipPAMClusteringRecommender.__doc__ = "Initial recommender selecting the medoids of a k-medoids clustering on an MI355X (stand-alone)."
 HipPAMClusteringRecommender.__module__ = __name__
 HipPAMClusteringRecommender.compatibility = "DISCRETE"
+
+
+# ---- k-means ---------------------------------------------------------------------------------------------------------------------
+def _is_int(value) -> bool:
+    return isinstance(value, (int, np.integer)) and not isinstance(value, bool)
+
+
+def _validate_kmeans(n_clusters, n_init, max_iter, tol, init, algorithm, sample_weight=None):
+    """scikit-learn's parameter validation in its words (``sklearn/utils/_param_validation.py``), then what the HIP path leaves out."""
+    if not (_is_int(n_clusters) and n_clusters >= 1):
+        raise ValueError(f"The 'n_clusters' parameter of KMeans must be an int in the range [1, inf). Got {n_clusters!r} instead.")
+    if not (_is_int(max_iter) and max_iter >= 1):
+        raise ValueError(f"The 'max_iter' parameter of KMeans must be an int in the range [1, inf). Got {max_iter!r} instead.")
+    if not ((isinstance(n_init, str) and n_init == "auto") or (_is_int(n_init) and n_init >= 1)):
+        raise ValueError(f"The 'n_init' parameter of KMeans must be a str among {{'auto'}} or an int in the range [1, inf). "
+                         f"Got {n_init!r} instead.")
+    if not (isinstance(tol, (int, float, np.integer, np.floating)) and not isinstance(tol, bool) and tol >= 0):
+        raise ValueError(f"The 'tol' parameter of KMeans must be a float in the range [0.0, inf). Got {tol!r} instead.")
+    if callable(init) or hasattr(init, "__array__") or isinstance(init, (list, tuple)):
+        raise ValueError("An array-like or callable init is not available on the HIP path; use 'k-means++' or 'random'.")
+    if not (isinstance(init, str) and init in ("k-means++", "random")):
+        raise ValueError(f"init needs to be 'k-means++' or 'random'. Got {init!r} instead.")
+    if algorithm == "elkan":
+        raise ValueError("algorithm='elkan' is not available on the HIP path; use 'lloyd'.")
+    if algorithm != "lloyd":
+        raise ValueError(f"algorithm needs to be 'lloyd' or 'elkan'. Got {algorithm!r} instead.")
+    if sample_weight is not None:
+        raise ValueError("Sample weights are not available on the HIP path.")
+
+
+def _same_clustering(labels, best, k: int) -> bool:
+    """``sklearn.cluster._k_means_common._is_same_clustering``: every label of ``labels`` meets a single label of ``best``."""
+    pairs = np.unique(labels.astype(np.int64) * k + best)
+    return len(np.unique(pairs // k)) == len(pairs)
+
+
+def _kmeans_fit(dev, n_clusters: int, n_init="auto", max_iter: int = 300, tol: float = 1e-4, init="k-means++", random_state=None,
+                algorithm="lloyd"):
+    """The contract of the module docstring on the selected rows of ``dev``: (centres, labels, inertia, n_iter, winning restart)."""
+    rs = _random_state(random_state)
+    N, k = dev.m, n_clusters
+    if k > N:
+        raise ValueError(f"n_samples={N} should be >= n_clusters={k}.")
+    R = (1 if init == "k-means++" else 10) if isinstance(n_init, str) else int(n_init)
+    if init == "random":
+        idx = np.stack([np.asarray(rs.choice(N, k, replace=False), dtype=np.int64) for _ in range(R)])
+    else:
+        T = 2 + int(np.log(k))
+        U = rs.random_sample((R, 1 + (k - 1) * T))
+        cdf = np.cumsum(np.full(N, 1.0 / N))
+        cdf /= cdf[-1]
+        first = np.minimum(np.searchsorted(cdf, U[:, 0], side="right"), N - 1).astype(np.int64)
+        idx = dev.kmeans_seed(first, U[:, 1:], k)
+    dev.kmeans_begin(idx)
+    threshold = tol * dev.mean_variance()
+    active = list(range(R))
+    n_iter, strict = np.zeros(R, dtype=np.int64), np.zeros(R, dtype=bool)
+    for _ in range(max_iter):
+        if not active:
+            break
+        same, shift = dev.kmeans_step(active)  # every still-running restart in one pass
+        n_iter[active] += 1
+        strict[np.asarray(active)[same]] = True
+        active = [r for a, r in enumerate(active) if not same[a] and not shift[a] <= threshold]
+    inertia = dev.kmeans_finish([r for r in range(R) if not strict[r]])
+    best, best_labels = 0, dev.kmeans_labels(0)
+    for r in range(1, R):
+        if inertia[r] < inertia[best]:
+            labels = dev.kmeans_labels(r)
+            if not _same_clustering(labels, best_labels, k):
+                best, best_labels = r, labels
+    distinct = len(np.unique(best_labels))
+    if distinct < k:
+        warnings.warn(f"Number of distinct clusters ({distinct}) found smaller than n_clusters ({k}). Possibly due to duplicate points "
+                      f"in X.", ConvergenceWarning, stacklevel=2)
+    return dev.kmeans_centres(best), best_labels, float(inertia[best]), int(n_iter[best]), best
+
+
+def k_means(points: np.ndarray, n_clusters: int, *, n_init="auto", max_iter: int = 300, tol: float = 1e-4, init="k-means++",
+            random_state=None, algorithm: str = "lloyd", device: int = 0, return_info: bool = False, sample_weight=None):
+    """``sklearn.cluster.KMeans(n_clusters, n_init=n_init, max_iter=max_iter, tol=tol, init=init, random_state=random_state)
+    .fit(points)`` on the device, all restarts as one workload: ``cluster_centers_`` [k, d].  With ``return_info`` also ``labels_``,
+    ``inertia_`` and ``n_iter_``.  ``n_init="auto"``: 1 for k-means++, 10 for random."""
+    _validate_kmeans(n_clusters, n_init, max_iter, tol, init, algorithm, sample_weight)  # refused before anything goes to the device
+    values = np.ascontiguousarray(points, dtype=np.float64)
+    if values.ndim != 2 or values.shape[0] < 1 or values.shape[1] < 1:
+        raise ValueError(f"Expected a 2D array with at least one row and one column, got an array of shape {values.shape}.")
+    if values.shape[1] > _MAX_D or values.shape[0] >= _MAX_ROWS:
+        raise ValueError(f"The HIP path takes at most {_MAX_D} columns and fewer than 2^31 - 256 rows, got {values.shape}.")
+    if n_clusters > values.shape[0]:
+        raise ValueError(f"n_samples={values.shape[0]} should be >= n_clusters={n_clusters}.")
+    rs = _random_state(random_state)
+    d = values.shape[1]
+    dev = _rows_factory(values, np.zeros(d), np.ones(d), device)  # (x - 0) / 1: the points themselves, bit for bit
+    centres, labels, inertia, n_iter, _ = _kmeans_fit(dev, n_clusters, n_init, max_iter, tol, init, rs, algorithm)
+    return (centres, labels, inertia, n_iter) if return_info else centres
+
+
+class HipKMeansRecommenderImpl(HipPAMRecommenderImpl):
+    """Behaviour of the k-means recommender on an MI355X, built like the k-medoids one: the resident matrix, its cache key, copying
+    and pickling are shared; the clustering is ``_kmeans_fit`` and the selection the reference's (the member nearest to each
+    centre)."""
+
+    __slots__ = ()
+
+    def _recommend_discrete(self, subspace_discrete, candidates_exp: pd.DataFrame, batch_size: int) -> pd.Index:
+        params = {"n_init": "auto", "max_iter": 300, "tol": 1e-4, "init": "k-means++", "algorithm": "lloyd", **self.model_params}
+        _validate_kmeans(batch_size, params["n_init"], params["max_iter"], params["tol"], params["init"], params["algorithm"])
+        dev, labels = self._resident_rows(subspace_discrete)
+        pos = None  # the candidates in their own row order (clustering.py:115-116)
+        if len(candidates_exp) != len(labels) or not candidates_exp.index.equals(labels):
+            pos = labels.get_indexer(candidates_exp.index)
+            if (pos < 0).any():
+                raise KeyError("candidates contain rows that are not part of the discrete subspace")
+        dev.select(pos)
+        centres, _, _, _, _ = _kmeans_fit(dev, batch_size, **params)
+        return candidates_exp.index[np.asarray(dev.kmeans_select(centres), dtype=np.int64)]
+
+
+def _check_kmeans_model_params(instance, attribute, value):
+    unknown = set(value) - {"n_init", "max_iter", "tol", "init", "random_state", "algorithm"}
+    if unknown:
+        raise TypeError(f"KMeans got unexpected model parameters: {sorted(unknown)}")
+
+
+def kmeans_recommender_fields() -> dict:
+    """attrs fields of the recommender: the reference's one (nonpredictive/clustering.py:207-214) plus the device and the cache."""
+    return {
+        "model_params": field(default=attrs.Factory(lambda: {"max_iter": 1000, "n_init": 50}),
+                              validator=[instance_of(dict), _check_kmeans_model_params]),
+        "device": field(default=0, validator=instance_of(int), kw_only=True),
+        "_fps_cache": field(default=None, init=False, eq=False, repr=False),
+    }
+
+
+class _StandAloneKMeans(HipKMeansRecommenderImpl, _StandAloneFPS):
+    """``recommend`` of the stand-alone FPS recommender over the k-means ``_recommend_discrete``."""
+
+    __slots__ = ()
+
+
+HipKMeansClusteringRecommender = attrs.make_class("HipKMeansClusteringRecommender", kmeans_recommender_fields(), bases=(_StandAloneKMeans,),
+                                                  slots=False)
+HipKMeansClusteringRecommender.__doc__ = ("Initial recommender selecting the member nearest to each centre of a k-means clustering on an "
+                                          "MI355X (stand-alone).")
+HipKMeansClusteringRecommender.__module__ = __name__
+HipKMeansClusteringRecommender.compatibility = "DISCRETE"

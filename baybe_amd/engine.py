@@ -1049,6 +1049,63 @@ class HipGP:
                                              flags.data_ptr()), "bbh_pam_update")
         return flags
 
+    # ---- k-means (baybe_amd.clustering): stateless, asynchronous, every buffer a device tensor, R restarts at once -
+    def kmeans_plan(self, d: int, k: int, R: int):
+        """(restarts per tile, chunks) of a pass over ``R`` restarts (``bbh_kmeans_plan``): that many restarts' centres share LDS,
+        so a point is read once per such tile; ``chunks > 1``: one restart per tile, its centres streamed through LDS."""
+        rt, chunks = C.c_int32(), C.c_int32()
+        self._check(self._lib.bbh_kmeans_plan(self._h, d, k, R, C.byref(rt), C.byref(chunks)), "bbh_kmeans_plan")
+        return rt.value, chunks.value
+
+    def kmeans_seed(self, P, M: int, idx, U, trials: int, closest=None):
+        """k-means++ for all restarts: fills the columns 1.. of ``idx [R, k]`` (int64 device tensor, column 0 = the first centres)
+        from the uniforms ``U [R, (k - 1) * trials]`` (``bbh_kmeans_seed``).  ``closest [R, M]``: work array (allocated if None)."""
+        torch = self._torch()
+        R, k = int(idx.shape[0]), int(idx.shape[1])
+        tiles = -(-M // 256)
+        if closest is None:
+            closest = torch.empty((R, M), dtype=torch.float64, device=P.device)
+        tilesum = torch.empty((R, tiles), dtype=torch.float64, device=P.device)
+        trialpart = torch.empty((R, trials, tiles), dtype=torch.float64, device=P.device)
+        cand = torch.empty((R, trials), dtype=torch.int64, device=P.device)
+        self._check(self._lib.bbh_kmeans_seed(self._h, P.data_ptr(), M, P.shape[0], P.stride(0), idx.data_ptr(),
+                                              None if U is None else U.data_ptr(), R, k, trials, closest.data_ptr(), tilesum.data_ptr(),
+                                              trialpart.data_ptr(), cand.data_ptr()), "bbh_kmeans_seed")
+        return idx
+
+    def kmeans_pass(self, P, M: int, centres, rid, labels, d2, out=None, want_sums: bool = True):
+        """One Lloyd pass (``bbh_kmeans_pass``) for the restarts ``rid`` (int32 device tensor) of ``centres [R, k, d]``: ``labels
+        [R, M]`` (int32) and ``d2 [R, M]`` are updated in place; returns the dict ``out`` of device tensors ``new`` [R, k, d], ``sums``
+        [R, k, d], ``counts`` [R, k] (int32), ``shift`` [R], ``inertia`` [R], ``flags`` [R] (int32: bit 0 = no label changed, bit 1 =
+        an empty cluster was met), allocated on the first call and passed back in on later ones.  Rows of restarts not in ``rid`` are
+        left as they are."""
+        torch = self._torch()
+        R, k, d = (int(s) for s in centres.shape)
+        if out is None:
+            dev = P.device
+            rt, _ = self.kmeans_plan(d, k, R)
+            tiles = -(-M // 256)
+            out = {"new": torch.zeros((R, k, d), dtype=torch.float64, device=dev), "sums": torch.zeros((R, k, d), dtype=torch.float64, device=dev),
+                   "counts": torch.zeros((R, k), dtype=torch.int32, device=dev), "shift": torch.zeros(R, dtype=torch.float64, device=dev),
+                   "inertia": torch.zeros(R, dtype=torch.float64, device=dev), "flags": torch.zeros(R, dtype=torch.int32, device=dev),
+                   "work_f64": torch.empty(tiles * rt * (k * d + 1), dtype=torch.float64, device=dev),
+                   "work_i32": torch.empty(tiles * rt * (k + 1), dtype=torch.int32, device=dev)}
+        self._check(self._lib.bbh_kmeans_pass(
+            self._h, P.data_ptr(), M, P.shape[0], P.stride(0), centres.data_ptr(), rid.data_ptr(), int(rid.shape[0]), k, int(want_sums),
+            labels.data_ptr(), d2.data_ptr(), out["work_f64"].data_ptr(), out["work_f64"].numel(), out["work_i32"].data_ptr(),
+            out["work_i32"].numel(), out["new"].data_ptr(), out["sums"].data_ptr(), out["counts"].data_ptr(), out["shift"].data_ptr(),
+            out["inertia"].data_ptr(), out["flags"].data_ptr()), "bbh_kmeans_pass")
+        return out
+
+    def kmeans_select(self, labels, d2, k: int):
+        """[k] int64 device tensor: per cluster the member with the smallest ``sqrt(d2)``, first on ties; 0 for a cluster without
+        members (``bbh_kmeans_select``).  ``labels`` [M] int32, ``d2`` [M]."""
+        torch = self._torch()
+        out = torch.empty(k, dtype=torch.int64, device=labels.device)
+        self._check(self._lib.bbh_kmeans_select(self._h, labels.data_ptr(), d2.data_ptr(), int(labels.shape[0]), k, out.data_ptr()),
+                    "bbh_kmeans_select")
+        return out
+
     # ---- row-sharded selection through the library's own RCCL communicator ---------------------------------
     def comm_unique_id(self) -> bytes:
         buf = C.create_string_buffer(256)

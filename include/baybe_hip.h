@@ -522,6 +522,36 @@ int bbh_pam_cost(bbh_handle* h, const double* Ps_dev, int64_t M, int32_t d, int6
 int bbh_pam_update(bbh_handle* h, const double* cost_dev, const int64_t* perm_dev, int64_t M, const int64_t* starts_dev, int64_t k,
                    int64_t* medoids_dev, int32_t* flags_dev);
 
+/* ---- k-means (Lloyd) over the matrix bbh_fps_prepare leaves, batched over R restarts (bbh_kmeans.hip) ---------------------------------
+ * The device side of sklearn.cluster.KMeans as KMeansClusteringRecommender drives it (nonpredictive/clustering.py:196-252), with the
+ * restarts as one workload.  d2(x, c) = sum_k (x_k - c_k) * (x_k - c_k), k ascending from 0.0, nothing contracted; a label is the
+ * smallest cluster index among equal minima; no floating-point atomics: every sum has a fixed order (a 256-position tile first, tiles
+ * ascending), so two runs give the same bits.  Limits of all: 1 <= M < 2^31 - 256, 1 <= d <= 768, 1 <= k <= M, R <= 65535.  All are
+ * asynchronous on the handle's stream and keep no state. */
+/* How a pass over R restarts is tiled: *restarts_per_tile restarts' centres share LDS (a point is read once per such tile);
+ * *chunks > 1: one restart per tile, its centres streamed through LDS in that many chunks (large k * d). */
+int bbh_kmeans_plan(bbh_handle* h, int32_t d, int64_t k, int64_t R, int32_t* restarts_per_tile, int32_t* chunks);
+/* k-means++ for R restarts at once.  idx_dev [R, k] int64: column 0 holds the first centres on entry, the rest is filled.  U_dev
+ * [R, (k - 1) * T]: the uniforms of the further centres, T per centre.  Per centre: pot = the sum of closest, the T values u * pot
+ * searched in the running sum of closest (first position that reaches it, clipped to M - 1), the candidate with the smallest new
+ * potential, first on ties.  Work arrays: closest_dev [R, M], tilesum_dev [R, tiles], trialpart_dev [R, T, tiles], cand_dev [R, T]
+ * int64, tiles = ceil(M / 256). */
+int bbh_kmeans_seed(bbh_handle* h, const double* P_dev, int64_t M, int32_t d, int64_t ldp, int64_t* idx_dev, const double* U_dev, int64_t R,
+                    int64_t k, int32_t T, double* closest_dev, double* tilesum_dev, double* trialpart_dev, int64_t* cand_dev);
+/* One Lloyd pass for the restarts rid_dev [n_active] int32 (indices into the [R, ...] arrays).  From C_dev [R, k, d]: labels_dev
+ * [R, M] int32 (read as the previous labels, then written), d2_dev [R, M] (to the assigned centre), inertia_dev [R]; with want_sums
+ * also sums_dev [R, k, d] and counts_dev [R, k] of the members, Cnew_dev [R, k, d] = sums / counts (the sum itself where the count
+ * is 0), shift_dev [R] = sum |new - old|^2.  flags_dev [R]: bit 0 = no label changed, bit 1 = an empty cluster was met.  Work
+ * arrays: tiles * restarts_per_tile * (k * d + 1) doubles and tiles * restarts_per_tile * (k + 1) ints (1 for k * d and k without
+ * want_sums). */
+int bbh_kmeans_pass(bbh_handle* h, const double* P_dev, int64_t M, int32_t d, int64_t ldp, const double* C_dev, const int32_t* rid_dev,
+                    int64_t n_active, int64_t k, int32_t want_sums, int32_t* labels_dev, double* d2_dev, double* work_f64_dev,
+                    int64_t work_f64_len, int32_t* work_i32_dev, int64_t work_i32_len, double* Cnew_dev, double* sums_dev,
+                    int32_t* counts_dev, double* shift_dev, double* inertia_dev, int32_t* flags_dev);
+/* The reference's selection without its [N, k] matrix: out_dev [k] int64 = per cluster the member with the smallest sqrt(d2), the
+ * smallest position among equal ones; 0 for a cluster without members (argmin of an all-infinite column). */
+int bbh_kmeans_select(bbh_handle* h, const int32_t* labels_dev, const double* d2_dev, int64_t M, int64_t k, int64_t* out_dev);
+
 /* The joint q'-batch and qLogNEHVI kernels split the MC samples into slices when a candidate set alone would not fill the chip; the
  * slice count - and with it the order in which a candidate's partial sums are added - follows the number of candidate rows.
  * rows > 0 fixes the row count the heuristic sees (a row shard passes the GLOBAL count: every rank then adds in the order the
