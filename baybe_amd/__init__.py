@@ -11,13 +11,15 @@ from baybe_amd._lib import HipError, HipUnavailableError, is_available, library_
 
 def __getattr__(name):
     """``farthest_point_sampling`` / ``HipFPSRecommender`` (``baybe_amd.sampling``) and ``k_medoids`` / ``HipPAMClusteringRecommender`` /
-    ``k_means`` / ``HipKMeansClusteringRecommender`` (``baybe_amd.clustering``), imported on first use: the modules pull in pandas and attrs, which a plain ``import baybe_amd`` does
+    ``k_means`` / ``HipKMeansClusteringRecommender`` / ``gaussian_mixture`` / ``HipGaussianMixtureClusteringRecommender``
+    (``baybe_amd.clustering``), imported on first use: the modules pull in pandas and attrs, which a plain ``import baybe_amd`` does
     not need."""
     if name in ("farthest_point_sampling", "HipFPSRecommender"):
         from baybe_amd import sampling
 
         return getattr(sampling, name)
-    if name in ("k_medoids", "HipPAMClusteringRecommender", "k_means", "HipKMeansClusteringRecommender"):
+    if name in ("k_medoids", "HipPAMClusteringRecommender", "k_means", "HipKMeansClusteringRecommender", "gaussian_mixture",
+                "HipGaussianMixtureClusteringRecommender"):
         from baybe_amd import clustering
 
         return getattr(clustering, name)
@@ -25,5 +27,6 @@ def __getattr__(name):
 
 
 __all__ = ["HipError", "HipUnavailableError", "is_available", "library_path", "farthest_point_sampling", "HipFPSRecommender", "k_medoids",
-           "HipPAMClusteringRecommender", "k_means", "HipKMeansClusteringRecommender"]
+           "HipPAMClusteringRecommender", "k_means", "HipKMeansClusteringRecommender", "gaussian_mixture",
+           "HipGaussianMixtureClusteringRecommender"]
 __version__ = "0.1.0"

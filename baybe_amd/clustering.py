@@ -1,5 +1,5 @@
-"""k-medoids and k-means clustering on the device, and the initial recommenders built on them (k-medoids first; the k-means
-contract follows it).
+"""k-medoids, k-means and Gaussian mixture clustering on the device, and the initial recommenders built on them (k-medoids first;
+the k-means and Gaussian mixture contracts follow it).
 
 ``k_medoids`` mirrors the reference's own ``KMedoids`` with ``method="alternate"``
 (``baybe/utils/clustering_algorithms/third_party/kmedoids.py``: same validation and error texts, same warnings, the same draws from the
@@ -83,6 +83,62 @@ cluster without members yields position 0, as ``argmin`` of an all-infinite colu
 
 ``max_iter = 0`` is a scikit-learn validation error in ``k_means`` and the recommender; the contract itself (``_kmeans_fit``, the
 oracle) covers it: no iteration, labels from the initial centres, ``n_iter = 0``.
+
+
+Gaussian mixture.  ``gaussian_mixture`` is the counterpart of ``sklearn.mixture.GaussianMixture(n_components, ...).fit`` as the
+reference's ``GaussianMixtureClusteringRecommender`` drives it (``nonpredictive/clustering.py:255-304``, ``model_params = {}``), and
+``HipGMMRecommenderImpl._recommend_discrete`` adds the selection that class really makes: ``_make_selection_default``
+(``clustering.py:55-76``) - the class does not set ``_use_custom_selector``, so its density selector is never run.  The kernels are
+in ``csrc/bbh_gmm.hip``.  As with k-means this is the project's own arithmetic, held to the oracle within a tolerance
+(``tests/_oracle_gmm.py`` restates it in numpy, from these words), not bit-parity with BLAS.
+
+Arguments and defaults.  ``n_components``, ``covariance_type="full"``, ``tol=1e-3``, ``reg_covar=1e-6``, ``max_iter=100``,
+``n_init=1``, ``init_params="kmeans"``, ``random_state=None``.  Generator: the one ``_random_state`` returns.
+
+Initialisation, per restart in restart order; a label of -1 marks a row of zeros.  ``"kmeans"``: the labels of the k-means contract
+above with ``n_init=1, max_iter=300, tol=1e-4, init="k-means++"``; a restart consumes ``1 + (k - 1) T`` uniforms whatever the data, so
+the draws of all R initialisations are taken up front as ``rs.random_sample((R, 1 + (k - 1) T))`` and run side by side as R restarts
+of one k-means pass - every restart's labels are used, none is chosen; scikit-learn's "distinct clusters" warning applies per
+restart.  ``"k-means++"``: the k positions of the k-means++ seeding of a restart, one-hot at those k rows only.
+``"random_from_data"``: ``rs.choice(N, k, replace=False)``, one-hot at those rows.  ``"random"`` is refused (it needs an [N, k]
+upload).
+
+M-step, from labels (one-hot) or from ``resp = exp(log_resp)``.  ``nk_c = sum_j r_jc + 10 * 2^-52``; ``mu_c = (sum_j r_jc x_j) /
+nk_c``; ``Sigma_c = (sum_j r_jc (x_j - mu_c)(x_j - mu_c)^T) / nk_c``, then ``+ reg_covar`` on the diagonal; ``w_c = nk_c / N``, and
+after an EM step ``w`` is also divided by ``sum_c w_c``, added in ascending c.
+
+Precision factor.  ``Sigma_c = L L^T`` (lower Cholesky); ``P_c = (L^-1)^T`` (upper triangular); ``logdet_c = sum_i log P_c[i, i]``
+(ascending i; the device carries the rounding error of every addition along, since d terms of one sign lose ulps of a large total).
+A pivot that is not finite and positive flags the restart, and the host raises scikit-learn's ``ValueError`` ("Fitting the mixture
+model failed because some components have ill-defined empirical covariance ...").
+
+E-step.  ``y = (x_j - mu_c) @ P_c`` and ``q = sum_i y_i^2``; ``lp_jc = -0.5 * (d * log(2 pi) + q) + logdet_c + log(w_c)``;
+``lpn_j = m + log(sum_c exp(lp_jc - m))`` with ``m = max_c lp_jc`` and c ascending; ``log_resp_jc = lp_jc - lpn_j``; ``label_j`` is
+the smallest c among equal maxima of ``lp_jc`` (this is ``predict``); ``lower_bound = (sum_j lpn_j) / N``.
+
+Loop, per restart, for ``n_iter = 1 .. max_iter``: E-step; M-step and precision factor; ``change = lb - prev`` with ``prev = -inf``
+at first; stop, converged, if ``|change| < tol``.  ``max_iter = 0`` keeps the initial parameters, ``n_iter = 0``, a lower bound of
+``-inf``, and gives no warning.
+
+Restart choice.  A restart replaces the best so far if its lower bound is strictly larger, or if nothing was kept yet.  If the
+winner did not converge and ``max_iter > 0``, scikit-learn's ``ConvergenceWarning`` is raised in its words ("Best performing
+initialization did not converge. ...").
+
+Prediction and selection.  One more E-step from the winner's parameters gives the labels; the member counts per component give the
+non-empty components, ascending; for each of them ``t = np.random.choice(count_c)`` - the GLOBAL generator, after the fit, consumed
+exactly as the reference's ``np.random.choice(members)`` consumes it - and the pick is the t-th member in position order.  A
+component without members yields no row: fewer than ``batch_size`` rows can come back.
+
+Fixed-shape sums.  Every sum has a fixed shape: positions ascending inside a strip of 256-position tiles, strips ascending, or the
+MFMA's own order, which the hardware fixes.  There are no floating-point atomics; two runs under one seed give the same bits.
+
+Refused before anything goes to the device: first scikit-learn's own texts for bad values of ``n_components``, ``tol``,
+``reg_covar``, ``max_iter``, ``n_init``, ``covariance_type`` and ``init_params``, for fewer than 2 samples and for ``n_samples <
+n_components``; then what the HIP path leaves out: a ``covariance_type`` other than ``"full"``, ``init_params="random"``,
+``weights_init`` / ``means_init`` / ``precisions_init``, ``warm_start``, more than 64 columns, and more than 65535 components (a
+grid dimension of the kernels).  The limit of 64 columns: full
+covariances cost ``k d^2`` doubles and their factorisation is one workgroup's work (64 x 64 doubles are 32 KB of LDS); wider comp
+reps go to k-means, whose limit stays 768.
 """
 
 from __future__ import annotations
@@ -297,6 +353,70 @@ class DeviceRows:
         self.gp.kmeans_pass(self.P, self.m, C, torch.zeros(1, dtype=torch.int32, device=dev), labels, d2, None, want_sums=False)
         return self.gp.kmeans_select(labels[0], d2[0], C.shape[1]).cpu().numpy()
 
+    # ---- Gaussian mixture: R restarts side by side.  Parameters [R, ...], log_resp [G, k, m] and labels [G, m] stay on the device. ----
+    def gmm_begin(self, k: int, reg_covar: float, idx=None):
+        """Starts R restarts with an M-step from labels - the labels the last k-means run left (``idx`` None), or the one-hot at the
+        positions ``idx`` [R, k] - and their precision factors: (components with members [R], failure flags [R], G = the restarts
+        that share a group, so that ``log_resp`` [G, k, m] stays under 1 GiB)."""
+        import torch
+
+        dev = self.P.device
+        if idx is None:
+            labels = self._km_labels
+        else:
+            pos = self._index(idx)
+            labels = torch.full((pos.shape[0], self.m), -1, dtype=torch.int32, device=dev)
+            labels.scatter_(1, pos, torch.arange(k, dtype=torch.int32, device=dev).expand(pos.shape[0], k).contiguous())
+        R = int(labels.shape[0])
+        self._gm = self.gp.gmm_params(R, k, self.d, dev)
+        self._gm_reg = float(reg_covar)
+        G = max(1, min(R, 2**30 // (8 * k * self.m)))
+        self._gm_lr = torch.empty((G, k, self.m), dtype=torch.float64, device=dev)
+        self._gm_lab = torch.empty((G, self.m), dtype=torch.int32, device=dev)
+        self.gp.gmm_mstep(self.P, self.m, self._gm, self._rid(np.arange(R)), reg_covar, labels=labels, normalize=False)
+        flat = labels.long() + torch.arange(R, device=dev)[:, None] * k
+        members = torch.bincount(flat[labels >= 0], minlength=R * k).view(R, k)
+        host = torch.cat([(members > 0).sum(1), self._gm["flags"].long()]).cpu().numpy()
+        return host[:R].copy(), host[R:].copy(), G
+
+    def gmm_step(self, active, base: int):
+        """One EM iteration of the restarts ``active`` (all inside the group that begins at restart ``base``): (lower bound of the
+        E-step [len(active)], failure flags after the M-step [len(active)]).  E-step, M-step and precision factors are enqueued back
+        to back; reading the bounds and flags is the one synchronisation."""
+        import torch
+
+        rid = self._rid(active)
+        self.gp.gmm_estep(self.P, self.m, self._gm, rid, self._gm_lr, self._gm_lab, base)
+        self.gp.gmm_mstep(self.P, self.m, self._gm, rid, self._gm_reg, log_resp=self._gm_lr, base=base, normalize=True)
+        rid = rid.long()
+        host = torch.cat([self._gm["lower"][rid], self._gm["flags"][rid].double()]).cpu().numpy()
+        return host[: len(active)].copy(), host[len(active):].astype(np.int64)
+
+    def gmm_predict(self, r: int):
+        """One more E-step from the parameters of restart ``r``: its labels stay on the device (``gmm_labels`` reads them)."""
+        self.gp.gmm_estep(self.P, self.m, self._gm, self._rid([r]), self._gm_lr, self._gm_lab, r)
+        self._gm_pred = self._gm_lab[0]
+
+    def gmm_labels(self) -> np.ndarray:
+        return self._gm_pred.cpu().numpy()
+
+    def gmm_result(self, r: int):
+        """(weights [k], means [k, d], covariances [k, d, d]) of restart ``r``."""
+        return tuple(self._gm[name][r].cpu().numpy() for name in ("w", "mu", "cov"))
+
+    def gmm_counts(self) -> np.ndarray:
+        """The member counts [k] of the predicted labels; the stable grouping behind them stays on the device for ``gmm_pick``."""
+        import torch
+
+        k = int(self._gm["w"].shape[1])
+        grouped, self._gm_perm = torch.sort(self._gm_pred, stable=True)  # position order kept inside a component
+        self._gm_starts = torch.searchsorted(grouped, torch.arange(k + 1, dtype=torch.int32, device=grouped.device))
+        return (self._gm_starts[1:] - self._gm_starts[:-1]).cpu().numpy()
+
+    def gmm_pick(self, components, t) -> np.ndarray:
+        """The positions of the ``t[i]``-th member, in position order, of the components ``components[i]``."""
+        return self._gm_perm[self._gm_starts[self._index(components)] + self._index(t)].cpu().numpy()
+
 
 _rows_factory = DeviceRows
 
@@ -509,9 +629,10 @@ def _same_clustering(labels, best, k: int) -> bool:
     return len(np.unique(pairs // k)) == len(pairs)
 
 
-def _kmeans_fit(dev, n_clusters: int, n_init="auto", max_iter: int = 300, tol: float = 1e-4, init="k-means++", random_state=None,
+def _kmeans_run(dev, n_clusters: int, n_init="auto", max_iter: int = 300, tol: float = 1e-4, init="k-means++", random_state=None,
                 algorithm="lloyd"):
-    """The contract of the module docstring on the selected rows of ``dev``: (centres, labels, inertia, n_iter, winning restart)."""
+    """Every restart of the contract of the module docstring on the selected rows of ``dev``, side by side: (inertia [R], n_iter
+    [R]); the restarts' labels and centres stay on ``dev``."""
     rs = _random_state(random_state)
     N, k = dev.m, n_clusters
     if k > N:
@@ -520,12 +641,7 @@ def _kmeans_fit(dev, n_clusters: int, n_init="auto", max_iter: int = 300, tol: f
     if init == "random":
         idx = np.stack([np.asarray(rs.choice(N, k, replace=False), dtype=np.int64) for _ in range(R)])
     else:
-        T = 2 + int(np.log(k))
-        U = rs.random_sample((R, 1 + (k - 1) * T))
-        cdf = np.cumsum(np.full(N, 1.0 / N))
-        cdf /= cdf[-1]
-        first = np.minimum(np.searchsorted(cdf, U[:, 0], side="right"), N - 1).astype(np.int64)
-        idx = dev.kmeans_seed(first, U[:, 1:], k)
+        idx = _kpp_positions(dev, k, R, rs)
     dev.kmeans_begin(idx)
     threshold = tol * dev.mean_variance()
     active = list(range(R))
@@ -537,7 +653,26 @@ def _kmeans_fit(dev, n_clusters: int, n_init="auto", max_iter: int = 300, tol: f
         n_iter[active] += 1
         strict[np.asarray(active)[same]] = True
         active = [r for a, r in enumerate(active) if not same[a] and not shift[a] <= threshold]
-    inertia = dev.kmeans_finish([r for r in range(R) if not strict[r]])
+    return dev.kmeans_finish([r for r in range(R) if not strict[r]]), n_iter
+
+
+def _kpp_positions(dev, k: int, R: int, rs) -> np.ndarray:
+    """The k-means++ centre positions [R, k] of R restarts from ``rs.random_sample((R, 1 + (k - 1) T))``."""
+    N = dev.m
+    T = 2 + int(np.log(k))
+    U = rs.random_sample((R, 1 + (k - 1) * T))
+    cdf = np.cumsum(np.full(N, 1.0 / N))
+    cdf /= cdf[-1]
+    first = np.minimum(np.searchsorted(cdf, U[:, 0], side="right"), N - 1).astype(np.int64)
+    return dev.kmeans_seed(first, U[:, 1:], k)
+
+
+def _kmeans_fit(dev, n_clusters: int, n_init="auto", max_iter: int = 300, tol: float = 1e-4, init="k-means++", random_state=None,
+                algorithm="lloyd"):
+    """The contract of the module docstring on the selected rows of ``dev``: (centres, labels, inertia, n_iter, winning restart)."""
+    k = n_clusters
+    inertia, n_iter = _kmeans_run(dev, n_clusters, n_init, max_iter, tol, init, random_state, algorithm)
+    R = len(inertia)
     best, best_labels = 0, dev.kmeans_labels(0)
     for r in range(1, R):
         if inertia[r] < inertia[best]:
@@ -620,3 +755,200 @@ HipKMeansClusteringRecommender.__doc__ = ("Initial recommender selecting the mem
                                           "MI355X (stand-alone).")
 HipKMeansClusteringRecommender.__module__ = __name__
 HipKMeansClusteringRecommender.compatibility = "DISCRETE"
+
+
+# ---- Gaussian mixture ------------------------------------------------------------------------------------------------------------
+_GMM_MAX_D = 64
+_GMM_MAX_K = 65535  # a grid dimension of the M-step and of the precision factor
+_COVARIANCE_TYPES = ("full", "tied", "diag", "spherical")
+_INIT_PARAMS = ("kmeans", "random", "random_from_data", "k-means++")
+_ILL_DEFINED = ("Fitting the mixture model failed because some components have ill-defined empirical covariance (for instance caused by "
+                "singleton or collapsed samples). Try to decrease the number of components, increase reg_covar, or scale the input data.")
+_NOT_CONVERGED = ("Best performing initialization did not converge. Try different init parameters, or increase max_iter, tol, or check "
+                  "for degenerate data.")
+
+
+def _is_real(value) -> bool:
+    return isinstance(value, (int, float, np.integer, np.floating)) and not isinstance(value, bool)
+
+
+def _validate_gmm(n_components, covariance_type="full", tol=1e-3, reg_covar=1e-6, max_iter=100, n_init=1, init_params="kmeans",
+                  weights_init=None, means_init=None, precisions_init=None, warm_start=False, shape=None):
+    """scikit-learn's parameter validation in its words and its (alphabetical) order, its two checks of the sample count, then what
+    the HIP path leaves out."""
+    def among(options):
+        return "{" + ", ".join(repr(o) for o in options) + "}"
+
+    if not (isinstance(covariance_type, str) and covariance_type in _COVARIANCE_TYPES):
+        raise ValueError(f"The 'covariance_type' parameter of GaussianMixture must be a str among {among(_COVARIANCE_TYPES)}. "
+                         f"Got {covariance_type!r} instead.")
+    if not (isinstance(init_params, str) and init_params in _INIT_PARAMS):
+        raise ValueError(f"The 'init_params' parameter of GaussianMixture must be a str among {among(_INIT_PARAMS)}. "
+                         f"Got {init_params!r} instead.")
+    if not (_is_int(max_iter) and max_iter >= 0):
+        raise ValueError(f"The 'max_iter' parameter of GaussianMixture must be an int in the range [0, inf). Got {max_iter!r} instead.")
+    if not (_is_int(n_components) and n_components >= 1):
+        raise ValueError(f"The 'n_components' parameter of GaussianMixture must be an int in the range [1, inf). "
+                         f"Got {n_components!r} instead.")
+    if not (_is_int(n_init) and n_init >= 1):
+        raise ValueError(f"The 'n_init' parameter of GaussianMixture must be an int in the range [1, inf). Got {n_init!r} instead.")
+    if not (_is_real(reg_covar) and reg_covar >= 0):
+        raise ValueError(f"The 'reg_covar' parameter of GaussianMixture must be a float in the range [0.0, inf). Got {reg_covar!r} instead.")
+    if not (_is_real(tol) and tol >= 0):
+        raise ValueError(f"The 'tol' parameter of GaussianMixture must be a float in the range [0.0, inf). Got {tol!r} instead.")
+    if shape is not None:
+        if shape[0] < 2:
+            raise ValueError(f"Found array with {shape[0]} sample(s) (shape={tuple(shape)}) while a minimum of 2 is required by "
+                             f"GaussianMixture.")
+        if shape[0] < n_components:
+            raise ValueError(f"Expected n_samples >= n_components but got n_components = {n_components}, n_samples = {shape[0]}")
+    if covariance_type != "full":
+        raise ValueError(f"covariance_type='{covariance_type}' is not available on the HIP path; only 'full' is.")
+    if init_params == "random":
+        raise ValueError("init_params='random' is not available on the HIP path (it needs an [N, k] upload); use 'kmeans', 'k-means++' "
+                         "or 'random_from_data'.")
+    if weights_init is not None or means_init is not None or precisions_init is not None:
+        raise ValueError("weights_init, means_init and precisions_init are not available on the HIP path.")
+    if warm_start:
+        raise ValueError("warm_start is not available on the HIP path.")
+    if shape is not None and shape[1] > _GMM_MAX_D:
+        raise ValueError(f"The HIP path takes at most {_GMM_MAX_D} columns for full covariances, got {shape[1]}; wider comp reps go to "
+                         f"k-means.")
+    if n_components > _GMM_MAX_K:
+        raise ValueError(f"The HIP path takes at most {_GMM_MAX_K} components, got {n_components}.")
+
+
+def _gmm_fit(dev, n_components: int, covariance_type="full", tol: float = 1e-3, reg_covar: float = 1e-6, max_iter: int = 100,
+             n_init: int = 1, init_params="kmeans", random_state=None):
+    """The Gaussian mixture contract of the module docstring on the selected rows of ``dev``: (weights, means, covariances, lower bound,
+    n_iter, converged, winning restart).  The winner's labels are predicted on ``dev`` (``dev.gmm_labels()``, ``_gmm_select``)."""
+    rs = _random_state(random_state)
+    N, k, R = dev.m, n_components, int(n_init)
+    _validate_gmm(k, covariance_type, tol, reg_covar, max_iter, R, init_params, shape=(N, dev.d))
+    if init_params == "kmeans":
+        _kmeans_run(dev, k, R, 300, 1e-4, "k-means++", rs)
+        distinct, flags, G = dev.gmm_begin(k, reg_covar)
+        for r in range(R):  # scikit-learn's warning, per restart
+            if distinct[r] < k:
+                warnings.warn(f"Number of distinct clusters ({distinct[r]}) found smaller than n_clusters ({k}). Possibly due to "
+                              f"duplicate points in X.", ConvergenceWarning, stacklevel=2)
+    else:
+        if init_params == "k-means++":
+            idx = _kpp_positions(dev, k, R, rs)
+        else:
+            idx = np.stack([np.asarray(rs.choice(N, k, replace=False), dtype=np.int64) for _ in range(R)])
+        _, flags, G = dev.gmm_begin(k, reg_covar, idx)
+    if flags.any():
+        raise ValueError(_ILL_DEFINED)
+    lower, n_iter, converged = np.full(R, -np.inf), np.zeros(R, dtype=np.int64), np.zeros(R, dtype=bool)
+    for base in range(0, R, G):  # the restarts of a group share log_resp
+        active = list(range(base, min(base + G, R)))
+        for _ in range(max_iter):
+            if not active:
+                break
+            lb, flags = dev.gmm_step(active, base)  # every still-running restart of the group in one pass
+            if flags.any():
+                raise ValueError(_ILL_DEFINED)
+            act = np.asarray(active)
+            change = lb - lower[act]
+            lower[act] = lb
+            n_iter[act] += 1
+            done = np.abs(change) < tol
+            converged[act[done]] = True
+            active = [r for a, r in enumerate(active) if not done[a]]
+    best = -1
+    for r in range(R):
+        if best < 0 or lower[r] > lower[best]:
+            best = r
+    if not converged[best] and max_iter > 0:
+        warnings.warn(_NOT_CONVERGED, ConvergenceWarning, stacklevel=2)
+    dev.gmm_predict(best)
+    weights, means, covariances = dev.gmm_result(best)
+    return weights, means, covariances, float(lower[best]), int(n_iter[best]), bool(converged[best]), best
+
+
+def _gmm_select(dev) -> np.ndarray:
+    """The reference's ``_make_selection_default`` (``nonpredictive/clustering.py:55-76``) on the labels ``dev`` predicted: one
+    ``np.random.choice`` among the members of every non-empty component, ascending - the global generator, consumed as the reference
+    consumes it.  Positions, fewer than the number of components if one is empty."""
+    counts = dev.gmm_counts()
+    components = np.flatnonzero(counts > 0)
+    t = np.array([np.random.choice(int(counts[c])) for c in components], dtype=np.int64)
+    return np.asarray(dev.gmm_pick(components, t), dtype=np.int64)
+
+
+def gaussian_mixture(points: np.ndarray, n_components: int, *, covariance_type="full", tol: float = 1e-3, reg_covar: float = 1e-6,
+                     max_iter: int = 100, n_init: int = 1, init_params="kmeans", random_state=None, weights_init=None, means_init=None,
+                     precisions_init=None, warm_start: bool = False, device: int = 0, return_info: bool = False):
+    """``sklearn.mixture.GaussianMixture(n_components, ...).fit(points)`` on the device, all restarts as one workload: ``(weights_,
+    means_, covariances_)``.  With ``return_info`` also the labels of ``predict(points)``, ``lower_bound_``, ``n_iter_`` and
+    ``converged_``."""
+    values = np.ascontiguousarray(points, dtype=np.float64)
+    if values.ndim != 2 or values.shape[1] < 1:
+        raise ValueError(f"Expected a 2D array with at least one column, got an array of shape {values.shape}.")
+    _validate_gmm(n_components, covariance_type, tol, reg_covar, max_iter, n_init, init_params, weights_init, means_init, precisions_init,
+                  warm_start, values.shape)  # refused before anything goes to the device
+    if values.shape[0] >= _MAX_ROWS:
+        raise ValueError(f"The HIP path takes fewer than 2^31 - 256 rows, got {values.shape}.")
+    rs = _random_state(random_state)
+    d = values.shape[1]
+    dev = _rows_factory(values, np.zeros(d), np.ones(d), device)  # (x - 0) / 1: the points themselves, bit for bit
+    weights, means, covariances, lower, n_iter, converged, _ = _gmm_fit(dev, n_components, covariance_type, tol, reg_covar, max_iter,
+                                                                        n_init, init_params, rs)
+    if return_info:
+        return weights, means, covariances, dev.gmm_labels(), lower, n_iter, converged
+    return weights, means, covariances
+
+
+class HipGMMRecommenderImpl(HipPAMRecommenderImpl):
+    """Behaviour of the Gaussian mixture recommender on an MI355X, built like the k-medoids one: the resident matrix, its cache key,
+    copying and pickling are shared; the clustering is ``_gmm_fit`` and the selection the reference's default one (a random member
+    of every non-empty component).  A component without members yields no row, so fewer than ``batch_size`` rows can come back, as
+    from the reference."""
+
+    __slots__ = ()
+
+    def _recommend_discrete(self, subspace_discrete, candidates_exp: pd.DataFrame, batch_size: int) -> pd.Index:
+        params = dict(self.model_params)
+        extra = {name: params.pop(name) for name in ("weights_init", "means_init", "precisions_init", "warm_start") if name in params}
+        _validate_gmm(batch_size, **{n: params[n] for n in params if n != "random_state"}, **extra,
+                      shape=(len(candidates_exp), subspace_discrete.comp_rep.shape[1]))
+        dev, labels = self._resident_rows(subspace_discrete)
+        pos = None  # the candidates in their own row order (clustering.py:115-116)
+        if len(candidates_exp) != len(labels) or not candidates_exp.index.equals(labels):
+            pos = labels.get_indexer(candidates_exp.index)
+            if (pos < 0).any():
+                raise KeyError("candidates contain rows that are not part of the discrete subspace")
+        dev.select(pos)
+        _gmm_fit(dev, batch_size, **params)
+        return candidates_exp.index[_gmm_select(dev)]
+
+
+def _check_gmm_model_params(instance, attribute, value):
+    unknown = set(value) - {"covariance_type", "tol", "reg_covar", "max_iter", "n_init", "init_params", "random_state", "weights_init",
+                            "means_init", "precisions_init", "warm_start"}
+    if unknown:
+        raise TypeError(f"GaussianMixture got unexpected model parameters: {sorted(unknown)}")
+
+
+def gmm_recommender_fields() -> dict:
+    """attrs fields of the recommender: the reference's one (nonpredictive/clustering.py:263-268) plus the device and the cache."""
+    return {
+        "model_params": field(default=attrs.Factory(dict), validator=[instance_of(dict), _check_gmm_model_params]),
+        "device": field(default=0, validator=instance_of(int), kw_only=True),
+        "_fps_cache": field(default=None, init=False, eq=False, repr=False),
+    }
+
+
+class _StandAloneGMM(HipGMMRecommenderImpl, _StandAloneFPS):
+    """``recommend`` of the stand-alone FPS recommender over the Gaussian mixture ``_recommend_discrete``."""
+
+    __slots__ = ()
+
+
+HipGaussianMixtureClusteringRecommender = attrs.make_class("HipGaussianMixtureClusteringRecommender", gmm_recommender_fields(),
+                                                           bases=(_StandAloneGMM,), slots=False)
+HipGaussianMixtureClusteringRecommender.__doc__ = ("Initial recommender selecting a random member of every component of a Gaussian "
+                                                   "mixture clustering on an MI355X (stand-alone).")
+HipGaussianMixtureClusteringRecommender.__module__ = __name__
+HipGaussianMixtureClusteringRecommender.compatibility = "DISCRETE"

@@ -1106,6 +1106,63 @@ class HipGP:
                     "bbh_kmeans_select")
         return out
 
+    # ---- Gaussian mixture (baybe_amd.clustering): stateless, asynchronous, every buffer a device tensor, R restarts at once -
+    def gmm_plan(self, d: int, k: int, M: int):
+        """(components per LDS chunk of the E-step, tiles per strip of the M-step) for ``M`` positions (``bbh_gmm_plan``)."""
+        kc, tps = C.c_int32(), C.c_int32()
+        self._check(self._lib.bbh_gmm_plan(self._h, d, k, M, C.byref(kc), C.byref(tps)), "bbh_gmm_plan")
+        return kc.value, tps.value
+
+    def gmm_params(self, R: int, k: int, d: int, device):
+        """The parameter arrays of ``R`` restarts, zeroed: the dict the other ``gmm_*`` calls read and write."""
+        torch = self._torch()
+        f = dict(dtype=torch.float64, device=device)
+        return {"nk": torch.zeros((R, k), **f), "w": torch.zeros((R, k), **f), "mu": torch.zeros((R, k, d), **f),
+                "cov": torch.zeros((R, k, d, d), **f), "prec": torch.zeros((R, k, d, d), **f), "logdet": torch.zeros((R, k), **f),
+                "lower": torch.zeros(R, **f), "flags": torch.zeros(R, dtype=torch.int32, device=device)}
+
+    def gmm_mstep(self, P, M: int, params, rid, reg_covar: float, log_resp=None, labels=None, base: int = 0, normalize: bool = True,
+                  work_limit: int = 1 << 25):
+        """The M-step (``bbh_gmm_mstep``) for the restarts ``rid`` (int32 device tensor) from ``log_resp [G, k, M]`` or ``labels
+        [G, M]`` (restart r reads row r - ``base``), then the precision factors (``bbh_gmm_precision``); ``params`` is updated in place.
+        The restarts are taken in groups whose strip partials stay below ``work_limit`` doubles (256 MB)."""
+        torch = self._torch()
+        R, k, d = (int(s) for s in params["mu"].shape)
+        _, tps = self.gmm_plan(d, k, M)
+        tiles = -(-M // 256)
+        strips = -(-tiles // tps)
+        nb = -(-d // 16)
+        per = strips * k * (d + 1 + 256 * (nb * (nb + 1) // 2))
+        group = max(1, work_limit // per)
+        n = int(rid.shape[0])
+        work = torch.empty(per * min(group, n), dtype=torch.float64, device=P.device)
+        for a in range(0, n, group):
+            part = rid[a: a + group]
+            self._check(self._lib.bbh_gmm_mstep(
+                self._h, P.data_ptr(), M, P.shape[0], P.stride(0), None if log_resp is None else log_resp.data_ptr(),
+                None if labels is None else labels.data_ptr(), base, part.data_ptr(), int(part.shape[0]), k, float(reg_covar),
+                int(normalize), work.data_ptr(), work.numel(), params["nk"].data_ptr(), params["w"].data_ptr(), params["mu"].data_ptr(),
+                params["cov"].data_ptr()), "bbh_gmm_mstep")
+        self.gmm_precision(params, rid)
+
+    def gmm_precision(self, params, rid):
+        """``prec``, ``logdet`` and ``flags`` of ``params`` from its ``cov`` for the restarts ``rid`` (``bbh_gmm_precision``)."""
+        R, k, d = (int(s) for s in params["mu"].shape)
+        self._check(self._lib.bbh_gmm_precision(self._h, params["cov"].data_ptr(), rid.data_ptr(), int(rid.shape[0]), k, d,
+                                                params["prec"].data_ptr(), params["logdet"].data_ptr(), params["flags"].data_ptr()),
+                    "bbh_gmm_precision")
+
+    def gmm_estep(self, P, M: int, params, rid, log_resp, labels, base: int = 0, lpn=None):
+        """The E-step (``bbh_gmm_estep``) for the restarts ``rid``: ``log_resp [G, k, M]``, ``labels [G, M]`` (int32) and, if given,
+        ``lpn [G, M]`` are written at row r - ``base``, ``params["lower"]`` at r."""
+        torch = self._torch()
+        R, k, d = (int(s) for s in params["mu"].shape)
+        work = torch.empty(-(-M // 256) * int(rid.shape[0]), dtype=torch.float64, device=P.device)
+        self._check(self._lib.bbh_gmm_estep(
+            self._h, P.data_ptr(), M, P.shape[0], P.stride(0), params["w"].data_ptr(), params["mu"].data_ptr(), params["prec"].data_ptr(),
+            params["logdet"].data_ptr(), rid.data_ptr(), int(rid.shape[0]), k, base, log_resp.data_ptr(), labels.data_ptr(),
+            None if lpn is None else lpn.data_ptr(), work.data_ptr(), work.numel(), params["lower"].data_ptr()), "bbh_gmm_estep")
+
     # ---- row-sharded selection through the library's own RCCL communicator ---------------------------------
     def comm_unique_id(self) -> bytes:
         buf = C.create_string_buffer(256)

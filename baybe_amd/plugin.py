@@ -131,3 +131,27 @@ def make_baybe_kmeans_recommender(base=None, discrete_compatibility=None):
     recommender.compatibility = discrete_compatibility
     recommender.__module__ = __name__
     return recommender
+
+
+def make_baybe_gmm_recommender(base=None, discrete_compatibility=None):
+    """``HipGaussianMixtureClusteringRecommender`` as a subclass of BayBE's ``NonPredictiveRecommender``: the counterpart of BayBE's
+    ``GaussianMixtureClusteringRecommender`` (``baybe/recommenders/pure/nonpredictive/clustering.py:255-304``), built exactly as
+    ``make_baybe_pam_recommender`` builds its class - the base's ``recommend`` stays in charge and calls the overridden
+    ``_recommend_discrete``.
+
+    Without arguments the base is imported from ``baybe``; the parameters exist so that the layout can be tested against a replica."""
+    from baybe_amd.clustering import HipGMMRecommenderImpl, gmm_recommender_fields
+
+    if base is None:
+        from baybe.recommenders.pure.nonpredictive.base import NonPredictiveRecommender as base
+    if discrete_compatibility is None:
+        from baybe.searchspace.core import SearchSpaceType
+
+        discrete_compatibility = SearchSpaceType.DISCRETE
+    recommender = attrs.make_class("HipGaussianMixtureClusteringRecommender", gmm_recommender_fields(), bases=(HipGMMRecommenderImpl, base),
+                                   slots=False)
+    recommender.__doc__ = ("Initial recommender selecting a random member of every component of a Gaussian mixture clustering on an "
+                           "MI355X (``baybe.recommenders.pure.nonpredictive.base.NonPredictiveRecommender``).")
+    recommender.compatibility = discrete_compatibility
+    recommender.__module__ = __name__
+    return recommender

@@ -552,6 +552,37 @@ int bbh_kmeans_pass(bbh_handle* h, const double* P_dev, int64_t M, int32_t d, in
  * smallest position among equal ones; 0 for a cluster without members (argmin of an all-infinite column). */
 int bbh_kmeans_select(bbh_handle* h, const int32_t* labels_dev, const double* d2_dev, int64_t M, int64_t k, int64_t* out_dev);
 
+/* ---- Gaussian mixture (EM, full covariances) over the matrix bbh_fps_prepare leaves, batched over R restarts (bbh_gmm.hip) -----------
+ * The device side of sklearn.mixture.GaussianMixture(n_components=batch_size) as GaussianMixtureClusteringRecommender drives it
+ * (nonpredictive/clustering.py:255-304).  Parameters live in [R, ...] arrays indexed by restart: w [R, k], mu [R, k, d], cov and prec
+ * [R, k, d, d] (row-major; prec upper triangular), logdet [R, k], nk [R, k]; rid_dev [n_active] int32 lists the restarts a call works
+ * on.  log_resp [G, k, M] is component-major and labels [G, M] int32; restart r uses row r - base of both.  No floating-point
+ * atomics: every sum has a fixed order (positions ascending inside a strip of 256-position tiles, strips ascending, or the MFMA's own
+ * order), so two runs give the same bits.  Limits of all: 1 <= M < 2^31 - 256, 1 <= d <= 64, 1 <= k <= min(M, 65535), restarts
+ * <= 65535.  All are asynchronous on the handle's stream and keep no state. */
+/* The form a shape takes: *comps_per_chunk components' P_c and mu_c share LDS in the E-step; a workgroup of the M-step owns
+ * *tiles_per_strip consecutive tiles (at most 64 strips, whatever M is). */
+int bbh_gmm_plan(bbh_handle* h, int32_t d, int64_t k, int64_t M, int32_t* comps_per_chunk, int32_t* tiles_per_strip);
+/* _estimate_gaussian_parameters + the weights of _m_step (sklearn/mixture/_gaussian_mixture.py:153-179, 258-294, 819-835).  r_jc =
+ * exp(log_resp_dev) or the one-hot of labels_dev (-1: a row of zeros); exactly one of the two is given.  nk_c = sum_j r_jc + 10 * 2^-52,
+ * mu_c = sum_j r_jc x_j / nk_c, cov_c = sum_j r_jc (x_j - mu_c)(x_j - mu_c)^T / nk_c + reg_covar I, w_c = nk_c / M, with normalize
+ * also divided by sum_c w_c (ascending c).  work_dev: strips * n_active * k * (d + 1 + 256 * b (b + 1) / 2) doubles, b = ceil(d / 16). */
+int bbh_gmm_mstep(bbh_handle* h, const double* P_dev, int64_t M, int32_t d, int64_t ldp, const double* log_resp_dev,
+                  const int32_t* labels_dev, int64_t src_base, const int32_t* rid_dev, int64_t n_active, int64_t k, double reg_covar,
+                  int32_t normalize, double* work_dev, int64_t work_len, double* nk_dev, double* w_dev, double* mu_dev, double* cov_dev);
+/* _compute_precision_cholesky + _compute_log_det_cholesky (_gaussian_mixture.py:297-351, 362-396): cov_c = L L^T, prec_c = (L^-1)^T,
+ * logdet_c = sum_i log prec_c[i][i].  A pivot that is not finite and positive sets bit 0 of flags_dev [R] (int32, zeroed by the
+ * caller): the host raises scikit-learn's ValueError. */
+int bbh_gmm_precision(bbh_handle* h, const double* cov_dev, const int32_t* rid_dev, int64_t n_active, int64_t k, int32_t d,
+                      double* prec_dev, double* logdet_dev, int32_t* flags_dev);
+/* _e_step / predict (sklearn/mixture/_base.py:296-313, 359-395; _gaussian_mixture.py:413-512): y = (x_j - mu_c) prec_c, lp_jc =
+ * -0.5 (d log 2 pi + |y|^2) + logdet_c + log w_c, lpn_j = m + log sum_c exp(lp_jc - m) with m = max_c lp_jc, log_resp_dev = lp - lpn,
+ * labels_dev = the smallest c among equal maxima of lp, lpn_dev [G, M] (may be null) = lpn, lower_dev [R] = sum_j lpn_j / M.  work_dev:
+ * tiles * n_active doubles. */
+int bbh_gmm_estep(bbh_handle* h, const double* P_dev, int64_t M, int32_t d, int64_t ldp, const double* w_dev, const double* mu_dev,
+                  const double* prec_dev, const double* logdet_dev, const int32_t* rid_dev, int64_t n_active, int64_t k, int64_t dst_base,
+                  double* log_resp_dev, int32_t* labels_dev, double* lpn_dev, double* work_dev, int64_t work_len, double* lower_dev);
+
 /* The joint q'-batch and qLogNEHVI kernels split the MC samples into slices when a candidate set alone would not fill the chip; the
  * slice count - and with it the order in which a candidate's partial sums are added - follows the number of candidate rows.
  * rows > 0 fixes the row count the heuristic sees (a row shard passes the GLOBAL count: every rank then adds in the order the
