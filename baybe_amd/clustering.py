@@ -511,11 +511,7 @@ def k_medoids(points: np.ndarray, n_clusters: int, max_iter: int = 100, init="k-
     """The reference's ``KMedoids(n_clusters, init=init, max_iter=max_iter, random_state=random_state).fit(points)`` on the device: the
     medoid positions in cluster order (``medoid_indices_``).  With ``return_info`` also ``labels_``, ``inertia_`` and ``n_iter_``."""
     _validate(n_clusters, max_iter, init, method, metric)  # refused before anything goes to the device
-    values = np.ascontiguousarray(points, dtype=np.float64)
-    if values.ndim != 2 or values.shape[0] < 1 or values.shape[1] < 1:
-        raise ValueError(f"Expected a 2D array with at least one row and one column, got an array of shape {values.shape}.")
-    if values.shape[1] > _MAX_D or values.shape[0] >= _MAX_ROWS:
-        raise ValueError(f"The HIP path takes at most {_MAX_D} columns and fewer than 2^31 - 256 rows, got {values.shape}.")
+    values = _as_points(points, _MAX_D)
     if n_clusters > values.shape[0]:
         raise ValueError("The number of medoids (%d) must be less than the number of samples %d." % (n_clusters, values.shape[0]))
     rs = _random_state(random_state)
@@ -524,6 +520,38 @@ def k_medoids(points: np.ndarray, n_clusters: int, max_iter: int = 100, init="k-
     medoids, labels, inertia, n_iter = _cluster(dev, n_clusters, max_iter, init, rs, method, metric)
     medoids = [int(i) for i in medoids]
     return (medoids, labels, inertia, n_iter) if return_info else medoids
+
+
+def _candidate_positions(labels: pd.Index, candidates_exp: pd.DataFrame):
+    """The positions of the candidates, in their own row order (clustering.py:115-116), in the resident matrix whose rows carry
+    ``labels``; ``None`` if the candidates are all of its rows in its order."""
+    if len(candidates_exp) == len(labels) and candidates_exp.index.equals(labels):
+        return None
+    pos = labels.get_indexer(candidates_exp.index)
+    if (pos < 0).any():
+        raise KeyError("candidates contain rows that are not part of the discrete subspace")
+    return pos
+
+
+def _as_points(points, max_d=None, min_rows: int = 1) -> np.ndarray:
+    """``points`` as a contiguous fp64 matrix, refused in the words of the public functions: not two-dimensional or too few rows /
+    columns, then (``max_d`` given) beyond the limits of the HIP path."""
+    values = np.ascontiguousarray(points, dtype=np.float64)
+    if values.ndim != 2 or values.shape[0] < min_rows or values.shape[1] < 1:
+        need = "at least one row and one column" if min_rows else "at least one column"
+        raise ValueError(f"Expected a 2D array with {need}, got an array of shape {values.shape}.")
+    if max_d is not None and (values.shape[1] > max_d or values.shape[0] >= _MAX_ROWS):
+        raise ValueError(f"The HIP path takes at most {max_d} columns and fewer than 2^31 - 256 rows, got {values.shape}.")
+    return values
+
+
+def _recommender_fields(default_params: dict, check) -> dict:
+    """attrs fields of a clustering recommender: the reference's ``model_params`` plus the device and the cache."""
+    return {
+        "model_params": field(default=attrs.Factory(lambda: dict(default_params)), validator=[instance_of(dict), check]),
+        "device": field(default=0, validator=instance_of(int), kw_only=True),
+        "_fps_cache": field(default=None, init=False, eq=False, repr=False),
+    }
 
 
 class HipPAMRecommenderImpl(HipFPSRecommenderImpl):
@@ -553,12 +581,7 @@ class HipPAMRecommenderImpl(HipFPSRecommenderImpl):
 
     def _recommend_discrete(self, subspace_discrete, candidates_exp: pd.DataFrame, batch_size: int) -> pd.Index:
         dev, labels = self._resident_rows(subspace_discrete)
-        pos = None  # the candidates in their own row order (clustering.py:115-116)
-        if len(candidates_exp) != len(labels) or not candidates_exp.index.equals(labels):
-            pos = labels.get_indexer(candidates_exp.index)
-            if (pos < 0).any():
-                raise KeyError("candidates contain rows that are not part of the discrete subspace")
-        dev.select(pos)
+        dev.select(_candidate_positions(labels, candidates_exp))
         medoids, _, _, _ = _cluster(dev, batch_size, **self.model_params)
         return candidates_exp.index[np.asarray(medoids, dtype=np.int64)]
 
@@ -573,13 +596,8 @@ def _check_model_params(instance, attribute, value):
 
 
 def pam_recommender_fields() -> dict:
-    """attrs fields of the recommender: the reference's one (nonpredictive/clustering.py:159-165) plus the device and the cache."""
-    return {
-        "model_params": field(default=attrs.Factory(lambda: {"max_iter": 100, "init": "k-medoids++"}),
-                              validator=[instance_of(dict), _check_model_params]),
-        "device": field(default=0, validator=instance_of(int), kw_only=True),
-        "_fps_cache": field(default=None, init=False, eq=False, repr=False),
-    }
+    """The reference's default (nonpredictive/clustering.py:159-165)."""
+    return _recommender_fields({"max_iter": 100, "init": "k-medoids++"}, _check_model_params)
 
 
 class _StandAlonePAM(HipPAMRecommenderImpl, _StandAloneFPS):
@@ -692,11 +710,7 @@ def k_means(points: np.ndarray, n_clusters: int, *, n_init="auto", max_iter: int
     .fit(points)`` on the device, all restarts as one workload: ``cluster_centers_`` [k, d].  With ``return_info`` also ``labels_``,
     ``inertia_`` and ``n_iter_``.  ``n_init="auto"``: 1 for k-means++, 10 for random."""
     _validate_kmeans(n_clusters, n_init, max_iter, tol, init, algorithm, sample_weight)  # refused before anything goes to the device
-    values = np.ascontiguousarray(points, dtype=np.float64)
-    if values.ndim != 2 or values.shape[0] < 1 or values.shape[1] < 1:
-        raise ValueError(f"Expected a 2D array with at least one row and one column, got an array of shape {values.shape}.")
-    if values.shape[1] > _MAX_D or values.shape[0] >= _MAX_ROWS:
-        raise ValueError(f"The HIP path takes at most {_MAX_D} columns and fewer than 2^31 - 256 rows, got {values.shape}.")
+    values = _as_points(points, _MAX_D)
     if n_clusters > values.shape[0]:
         raise ValueError(f"n_samples={values.shape[0]} should be >= n_clusters={n_clusters}.")
     rs = _random_state(random_state)
@@ -717,12 +731,7 @@ class HipKMeansRecommenderImpl(HipPAMRecommenderImpl):
         params = {"n_init": "auto", "max_iter": 300, "tol": 1e-4, "init": "k-means++", "algorithm": "lloyd", **self.model_params}
         _validate_kmeans(batch_size, params["n_init"], params["max_iter"], params["tol"], params["init"], params["algorithm"])
         dev, labels = self._resident_rows(subspace_discrete)
-        pos = None  # the candidates in their own row order (clustering.py:115-116)
-        if len(candidates_exp) != len(labels) or not candidates_exp.index.equals(labels):
-            pos = labels.get_indexer(candidates_exp.index)
-            if (pos < 0).any():
-                raise KeyError("candidates contain rows that are not part of the discrete subspace")
-        dev.select(pos)
+        dev.select(_candidate_positions(labels, candidates_exp))
         centres, _, _, _, _ = _kmeans_fit(dev, batch_size, **params)
         return candidates_exp.index[np.asarray(dev.kmeans_select(centres), dtype=np.int64)]
 
@@ -734,13 +743,8 @@ def _check_kmeans_model_params(instance, attribute, value):
 
 
 def kmeans_recommender_fields() -> dict:
-    """attrs fields of the recommender: the reference's one (nonpredictive/clustering.py:207-214) plus the device and the cache."""
-    return {
-        "model_params": field(default=attrs.Factory(lambda: {"max_iter": 1000, "n_init": 50}),
-                              validator=[instance_of(dict), _check_kmeans_model_params]),
-        "device": field(default=0, validator=instance_of(int), kw_only=True),
-        "_fps_cache": field(default=None, init=False, eq=False, repr=False),
-    }
+    """The reference's default (nonpredictive/clustering.py:207-214)."""
+    return _recommender_fields({"max_iter": 1000, "n_init": 50}, _check_kmeans_model_params)
 
 
 class _StandAloneKMeans(HipKMeansRecommenderImpl, _StandAloneFPS):
@@ -883,9 +887,7 @@ def gaussian_mixture(points: np.ndarray, n_components: int, *, covariance_type="
     """``sklearn.mixture.GaussianMixture(n_components, ...).fit(points)`` on the device, all restarts as one workload: ``(weights_,
     means_, covariances_)``.  With ``return_info`` also the labels of ``predict(points)``, ``lower_bound_``, ``n_iter_`` and
     ``converged_``."""
-    values = np.ascontiguousarray(points, dtype=np.float64)
-    if values.ndim != 2 or values.shape[1] < 1:
-        raise ValueError(f"Expected a 2D array with at least one column, got an array of shape {values.shape}.")
+    values = _as_points(points, min_rows=0)
     _validate_gmm(n_components, covariance_type, tol, reg_covar, max_iter, n_init, init_params, weights_init, means_init, precisions_init,
                   warm_start, values.shape)  # refused before anything goes to the device
     if values.shape[0] >= _MAX_ROWS:
@@ -914,12 +916,7 @@ class HipGMMRecommenderImpl(HipPAMRecommenderImpl):
         _validate_gmm(batch_size, **{n: params[n] for n in params if n != "random_state"}, **extra,
                       shape=(len(candidates_exp), subspace_discrete.comp_rep.shape[1]))
         dev, labels = self._resident_rows(subspace_discrete)
-        pos = None  # the candidates in their own row order (clustering.py:115-116)
-        if len(candidates_exp) != len(labels) or not candidates_exp.index.equals(labels):
-            pos = labels.get_indexer(candidates_exp.index)
-            if (pos < 0).any():
-                raise KeyError("candidates contain rows that are not part of the discrete subspace")
-        dev.select(pos)
+        dev.select(_candidate_positions(labels, candidates_exp))
         _gmm_fit(dev, batch_size, **params)
         return candidates_exp.index[_gmm_select(dev)]
 
@@ -932,12 +929,8 @@ def _check_gmm_model_params(instance, attribute, value):
 
 
 def gmm_recommender_fields() -> dict:
-    """attrs fields of the recommender: the reference's one (nonpredictive/clustering.py:263-268) plus the device and the cache."""
-    return {
-        "model_params": field(default=attrs.Factory(dict), validator=[instance_of(dict), _check_gmm_model_params]),
-        "device": field(default=0, validator=instance_of(int), kw_only=True),
-        "_fps_cache": field(default=None, init=False, eq=False, repr=False),
-    }
+    """The reference's default (nonpredictive/clustering.py:263-268)."""
+    return _recommender_fields({}, _check_gmm_model_params)
 
 
 class _StandAloneGMM(HipGMMRecommenderImpl, _StandAloneFPS):

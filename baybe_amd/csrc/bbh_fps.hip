@@ -20,23 +20,16 @@
 //   bbh_fps_pick_kernel          one workgroup: global maximum of the chunk keys, the count of bit-equal rows, and the k-th of them
 //                                in rank order (k < 0: the last one).
 //
-// The deciding value is always  d^2(x, y) = sum_k (x_k - y_k) * (x_k - y_k),  k ascending from 0.0, subtract / multiply / add each
-// rounded to fp64: contraction is off for the whole file, so no v_fma_f64 appears in the distance loops and every comparison of two
-// distances sees the bits a numpy loop over k produces.  (x - y)^2 is symmetric bit for bit, so d^2(i, j) == d^2(j, i).
-// Tie rules, all in ranks: the farthest pair is the smallest a, then the smallest b, over a < b; a greedy pick is the k-th row in
-// rank order among the bit-equal maxima.  Dead (masked) rows: NaN in the staged j tile (NaN > x is false) and mind = -inf.
-#include <math.h>
+// The deciding value is always d^2 by the arithmetic contract of bbh_rows.h (the generic pair walk, the chain between two columns
+// and the key reduction come from there).  Tie rules, all in ranks: the farthest pair is the smallest a, then the smallest b, over a < b; a
+// greedy pick is the k-th row in rank order among the bit-equal maxima.  Dead (masked) rows: NaN in the staged j tile (NaN > x is
+// false) and mind = -inf.
 #include <string.h>
 
-#include "bbh_common.h"
+#include "bbh_rows.h"
 
-#pragma clang fp contract(off)
-
-#define FPS_TI 256          // rows i per workgroup (one per thread)
-#define FPS_TJ 64           // rows j per LDS tile of the register form
-#define FPS_MAX_SEGS 64     // segments of j per tile of i (bounds the key count: tiles x segments)
-#define FPS_MAX_D 768       // generic form: an 8-row j tile of d columns within the default LDS limit
-#define FPS_MAX_ROWS 2147483392ll  // ranks are 32-bit inside the kernels (2^31 - 256)
+#define FPS_TI BBH_ROWS_TILE  // rows i per workgroup (one per thread)
+#define FPS_MAX_SEGS 64       // segments of j per tile of i (bounds the key count: tiles x segments)
 
 namespace {
 
@@ -75,30 +68,15 @@ fps_state* fps_get(bbh_handle* h) {
 }
 
 // (d^2 descending, a ascending, b ascending): does x beat y?  b < 0 marks an empty key.
-__device__ __forceinline__ bool fps_pair_beats(double xv, int xa, int xb, double yv, int ya, int yb) {
-  if (xb < 0) return false;
-  if (yb < 0) return true;
-  return xv > yv || (xv == yv && (xa < ya || (xa == ya && xb < yb)));
-}
-
-__device__ __forceinline__ void fps_pair_block_best(double& v, int& a, int& b, double* sv, int* sa, int* sb) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const double ov = __shfl_xor(v, o, 64);
-    const int oa = __shfl_xor(a, o, 64);
-    const int ob = __shfl_xor(b, o, 64);
-    if (fps_pair_beats(ov, oa, ob, v, a, b)) v = ov, a = oa, b = ob;
-  }
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) {
-    sv[threadIdx.x >> 6] = v;
-    sa[threadIdx.x >> 6] = a;
-    sb[threadIdx.x >> 6] = b;
-  }
-  __syncthreads();
-  v = sv[0], a = sa[0], b = sb[0];
-  for (int w = 1; w < 4; w++)
-    if (fps_pair_beats(sv[w], sa[w], sb[w], v, a, b)) v = sv[w], a = sa[w], b = sb[w];
+struct FpsPairKey {
+  double v;
+  int a, b;
+  __device__ __forceinline__ FpsPairKey shfl_xor(int o) const { return {__shfl_xor(v, o, 64), __shfl_xor(a, o, 64), __shfl_xor(b, o, 64)}; }
+};
+__device__ __forceinline__ bool fps_pair_beats(const FpsPairKey& x, const FpsPairKey& y) {
+  if (x.b < 0) return false;
+  if (y.b < 0) return true;
+  return x.v > y.v || (x.v == y.v && (x.a < y.a || (x.a == y.a && x.b < y.b)));
 }
 
 }  // namespace
@@ -131,12 +109,65 @@ struct FpsPairArgs {
   int* key_b;
 };
 
+namespace {
+
+// a j beyond the segment or a dead j is staged as NaN: visited, and never a maximum
+struct FpsPairLoad {
+  static constexpr bool whole_tiles = true;
+  const uint8_t* alive;
+  int seg1;
+  __device__ __forceinline__ bool live(int j) const { return j < seg1 && (!alive || alive[j]); }
+  __device__ __forceinline__ double pad() const { return NAN; }
+};
+
+// The workgroup's share of the pairs: rows i of tile blockIdx.y against the rows j > i of segment blockIdx.x (multiples of 64 at
+// both ends but the last).  false: the segment lies below the tile's diagonal, an empty key.
+struct FpsPairRange {
+  int i0, i, j_begin, seg1;
+  bool live_i;
+  __device__ __forceinline__ bool set(const FpsPairArgs& A) {
+    i0 = blockIdx.y * FPS_TI, i = i0 + threadIdx.x;
+    const int seg0 = blockIdx.x * A.seg_rows;
+    seg1 = (A.M - seg0 < A.seg_rows) ? A.M : seg0 + A.seg_rows;  // (seg0 < M by the grid)
+    j_begin = (seg0 > i0) ? seg0 : i0;
+    live_i = i < A.M && (!A.alive || A.alive[i]);
+    return seg1 > i0 + 1;  // some j of the segment lies above the smallest i (uniform)
+  }
+};
+
+// the running maximum of a row: ascending j, strict >, so the smallest j of equal distances stays
+struct FpsPairVisit {
+  int i;
+  double& best;
+  int& bj;
+  __device__ __forceinline__ void operator()(int j, double d2, bool) const {
+    const bool take = (d2 > best) & (j > i);  // (two selects, no branch: the chains of a group stay in one block)
+    best = take ? d2 : best, bj = take ? j : bj;
+  }
+};
+
+// one key per workgroup
+__device__ __forceinline__ void fps_pairs_store(const FpsPairArgs& A, FpsPairKey* s_key, double best, int i, int bj) {
+  const FpsPairKey top = bbh_rows_block_best(FpsPairKey{best, i, bj}, s_key, fps_pair_beats);
+  if (threadIdx.x == 0) {
+    const int key = blockIdx.y * gridDim.x + blockIdx.x;
+    A.key_v[key] = top.v;
+    A.key_a[key] = top.a;
+    A.key_b[key] = top.b;
+  }
+}
+
+}  // namespace
+
+// The register form keeps a walk of its own - the one of bbh_rows_pair_walk with whole tiles, NaN for a dead or padded j and a
+// running maximum: written through the template the <12> instantiation takes 82 VGPRs instead of 80 (5 waves per SIMD instead of 6)
+// and the loops come out in another instruction order.  The key index is computed BEFORE the walk for the same reason: computed
+// after it, the same source compiles to 82 VGPRs as well.
 template <int DP>
 __global__ __launch_bounds__(256) void bbh_fps_pairs_kernel(const FpsPairArgs A) {
-  __shared__ double s_x[FPS_TJ * DP];  // [j][DP]
-  __shared__ double s_v[4];
-  __shared__ int s_a[4], s_b[4];
-  constexpr int NPRE = (FPS_TJ * DP + 255) / 256;
+  __shared__ double s_x[BBH_ROWS_TJ * DP];  // [j][DP]
+  __shared__ FpsPairKey s_key[4];
+  constexpr int NPRE = (BBH_ROWS_TJ * DP + 255) / 256;
   const int tid = threadIdx.x;
   const int i0 = blockIdx.y * FPS_TI;
   const int i = i0 + tid;
@@ -163,16 +194,16 @@ __global__ __launch_bounds__(256) void bbh_fps_pairs_kernel(const FpsPairArgs A)
       }
     };
     load(j0);
-    for (; j0 < seg1; j0 += FPS_TJ) {
+    for (; j0 < seg1; j0 += BBH_ROWS_TJ) {
       __syncthreads();
 #pragma unroll
       for (int u = 0; u < NPRE; u++) {
         const int e = tid + u * 256;
-        if (e < FPS_TJ * DP) s_x[(e & 63) * DP + (e >> 6)] = pre[u];
+        if (e < BBH_ROWS_TJ * DP) s_x[(e & 63) * DP + (e >> 6)] = pre[u];
       }
       __syncthreads();
-      if (j0 + FPS_TJ < seg1) load(j0 + FPS_TJ);  // in flight during the tile's arithmetic
-      for (int jj = 0; jj < FPS_TJ; jj += 4) {
+      if (j0 + BBH_ROWS_TJ < seg1) load(j0 + BBH_ROWS_TJ);  // in flight during the tile's arithmetic
+      for (int jj = 0; jj < BBH_ROWS_TJ; jj += 4) {
         const double* x0 = s_x + jj * DP;
         double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
 #pragma unroll
@@ -192,85 +223,39 @@ __global__ __launch_bounds__(256) void bbh_fps_pairs_kernel(const FpsPairArgs A)
     }
     if (!live_i) bj = -1;
   }
-  int ba = i;
-  fps_pair_block_best(best, ba, bj, s_v, s_a, s_b);
-  if (tid == 0) {
-    A.key_v[key] = best;
-    A.key_a[key] = ba;
-    A.key_b[key] = bj;
-  }
+  const FpsPairKey top = bbh_rows_block_best(FpsPairKey{best, i, bj}, s_key, fps_pair_beats);
+  if (tid == 0) A.key_v[key] = top.v, A.key_a[key] = top.a, A.key_b[key] = top.b;
 }
 
 // any d: LDS tile [k][TJ] (TJ in {8, 16, 32, 64}: tj_shift), dynamic LDS d * TJ doubles
 __global__ __launch_bounds__(256) void bbh_fps_pairs_generic_kernel(const FpsPairArgs A, int tj_shift) {
   extern __shared__ double s_xg[];
-  __shared__ double s_v[4];
-  __shared__ int s_a[4], s_b[4];
-  const int TJ = 1 << tj_shift;
-  const int tid = threadIdx.x;
-  const int i0 = blockIdx.y * FPS_TI;
-  const int i = i0 + tid;
-  const int seg0 = blockIdx.x * A.seg_rows;
-  const int seg1 = (A.M - seg0 < A.seg_rows) ? A.M : seg0 + A.seg_rows;
-  const int key = blockIdx.y * gridDim.x + blockIdx.x;
+  __shared__ FpsPairKey s_key[4];
+  FpsPairRange r;
   double best = -INFINITY;
   int bj = -1;
-  if (seg1 > i0 + 1) {
-    const bool live_i = i < A.M && (!A.alive || A.alive[i]);
-    const double* Pi = A.P + (live_i ? i : i0);  // (i0 < M by the grid: a valid address for the idle lanes)
-    for (int j0 = (seg0 > i0) ? seg0 : i0; j0 < seg1; j0 += TJ) {
-      __syncthreads();
-      for (int e = tid; e < A.d * TJ; e += 256) {
-        const int k = e >> tj_shift, j = j0 + (e & (TJ - 1));
-        s_xg[e] = (j < seg1 && (!A.alive || A.alive[j])) ? A.P[(int64_t)k * A.ldp + j] : NAN;
-      }
-      __syncthreads();
-      for (int jj = 0; jj < TJ; jj += 8) {
-        double acc[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-        for (int k = 0; k < A.d; k++) {
-          const double x = Pi[(int64_t)k * A.ldp];
-          const double* xs = s_xg + k * TJ + jj;
-#pragma unroll
-          for (int u = 0; u < 8; u++) {
-            const double t = x - xs[u];
-            acc[u] = acc[u] + t * t;
-          }
-        }
-#pragma unroll
-        for (int u = 0; u < 8; u++) {
-          const int j = j0 + jj + u;
-          if (acc[u] > best && j > i) best = acc[u], bj = j;
-        }
-      }
-    }
-    if (!live_i) bj = -1;
+  if (r.set(A)) {
+    const double* xi = A.P + (r.live_i ? r.i : r.i0);  // (i0 < M by the grid: a valid address for the idle lanes)
+    bbh_rows_pair_walk_generic(A.P, A.ldp, A.d, xi, r.j_begin, r.seg1, tj_shift, s_xg, FpsPairLoad{A.alive, r.seg1}, FpsPairVisit{r.i, best, bj});
+    if (!r.live_i) bj = -1;
   }
-  int ba = i;
-  fps_pair_block_best(best, ba, bj, s_v, s_a, s_b);
-  if (tid == 0) {
-    A.key_v[key] = best;
-    A.key_a[key] = ba;
-    A.key_b[key] = bj;
-  }
+  fps_pairs_store(A, s_key, best, r.i, bj);
 }
 
 // out: [d2 | a | b] as three 8-byte words (a = b = -1: fewer than two live rows)
 __global__ __launch_bounds__(256) void bbh_fps_pairs_final_kernel(const double* __restrict__ key_v, const int* __restrict__ key_a,
                                                                   const int* __restrict__ key_b, int64_t nkeys, double* __restrict__ out) {
-  __shared__ double s_v[4];
-  __shared__ int s_a[4], s_b[4];
-  double v = -INFINITY;
-  int a = -1, b = -1;
+  __shared__ FpsPairKey s_key[4];
+  FpsPairKey best = {-INFINITY, -1, -1};
   for (int64_t e = threadIdx.x; e < nkeys; e += 256) {
-    const double kv = key_v[e];
-    const int ka = key_a[e], kb = key_b[e];
-    if (fps_pair_beats(kv, ka, kb, v, a, b)) v = kv, a = ka, b = kb;
+    const FpsPairKey key = {key_v[e], key_a[e], key_b[e]};
+    if (fps_pair_beats(key, best)) best = key;
   }
-  fps_pair_block_best(v, a, b, s_v, s_a, s_b);
+  best = bbh_rows_block_best(best, s_key, fps_pair_beats);
   if (threadIdx.x == 0) {
-    out[0] = v;
-    ((int64_t*)out)[1] = (b >= 0) ? a : -1;
-    ((int64_t*)out)[2] = b;
+    out[0] = best.v;
+    ((int64_t*)out)[1] = (best.b >= 0) ? best.a : -1;
+    ((int64_t*)out)[2] = best.b;
   }
 }
 
@@ -292,11 +277,7 @@ __global__ __launch_bounds__(256) void bbh_fps_pass_kernel(const double* __restr
   if (r < M) {
     v = mind[r];
     if (have_c) {
-      double acc = 0.0;
-      for (int k = 0; k < d; k++) {
-        const double t = P[(int64_t)k * ldp + r] - P[(int64_t)k * ldp + c];
-        acc = acc + t * t;
-      }
+      const double acc = bbh_rows_d2(P, ldp, d, r, c);
       v = (r == c) ? -INFINITY : ((acc < v) ? acc : v);
       mind[r] = v;
     }
@@ -474,14 +455,6 @@ static int fps_results(bbh_handle* h, fps_state* st, size_t picks) {
   return 0;
 }
 
-static int fps_check_matrix(bbh_handle* h, const char* who, const double* P_dev, int64_t M, int32_t d, int64_t ldp) {
-  if (!P_dev || M < 1 || M > FPS_MAX_ROWS || d < 1 || ldp < M) {
-    h->err = std::string(who) + ": bad arguments (need P_dev, 1 <= M < 2^31, d >= 1, ldp >= M)";
-    return -1;
-  }
-  return 0;
-}
-
 extern "C" int bbh_fps_prepare(bbh_handle* h, const double* X_dev, int64_t N, int32_t d, int64_t ldx, const double* mean_host,
                                const double* scale_host, const int64_t* order_dev, int64_t M, double* P_dev, int64_t ldp) {
   if (!h) return -1;
@@ -506,18 +479,13 @@ extern "C" int bbh_fps_prepare(bbh_handle* h, const double* X_dev, int64_t N, in
   return 0;
 }
 
-template <int DP>
-static void fps_launch_pairs(bbh_handle* h, dim3 grid, const FpsPairArgs& a) {
-  hipLaunchKernelGGL(bbh_fps_pairs_kernel<DP>, grid, dim3(256), 0, h->stream, a);
-}
-
 extern "C" int bbh_fps_farthest_pair(bbh_handle* h, const double* P_dev, int64_t M, int32_t d, int64_t ldp, const uint8_t* alive_dev,
                                      double* d2_host, int64_t* a_host, int64_t* b_host) {
   if (!h) return -1;
-  int rc = fps_check_matrix(h, "bbh_fps_farthest_pair", P_dev, M, d, ldp);
+  int rc = bbh_rows_check(h, "bbh_fps_farthest_pair", P_dev, M, d, ldp);
   if (rc) return rc;
-  if (!d2_host || !a_host || !b_host || M < 2 || d > FPS_MAX_D) {
-    h->err = "bbh_fps_farthest_pair: bad arguments (need M >= 2, d <= 768 and the three result pointers)";
+  if (!d2_host || !a_host || !b_host || M < 2) {
+    h->err = "bbh_fps_farthest_pair: bad arguments (need M >= 2 and the three result pointers)";
     return -1;
   }
   BBH_HIP_TRY(h, hipSetDevice(h->device));
@@ -546,19 +514,16 @@ extern "C" int bbh_fps_farthest_pair(bbh_handle* h, const double* P_dev, int64_t
   a.P = P_dev, a.ldp = ldp, a.M = (int)M, a.d = (int)d, a.seg_rows = (int)seg_rows, a.alive = alive_dev;
   a.key_v = st->d_key_v, a.key_a = st->d_key_a, a.key_b = st->d_key_b;
   const dim3 grid((unsigned)segs, (unsigned)tiles);
-  if (d <= 2) fps_launch_pairs<2>(h, grid, a);
-  else if (d <= 4) fps_launch_pairs<4>(h, grid, a);
-  else if (d <= 8) fps_launch_pairs<8>(h, grid, a);
-  else if (d <= 12) fps_launch_pairs<12>(h, grid, a);
-  else if (d <= 16) fps_launch_pairs<16>(h, grid, a);
-  else if (d <= 20) fps_launch_pairs<20>(h, grid, a);
-  else if (d <= 24) fps_launch_pairs<24>(h, grid, a);
-  else if (d <= 32) fps_launch_pairs<32>(h, grid, a);
-  else {
-    const int tj_shift = (d <= 96) ? 6 : (d <= 192) ? 5 : (d <= 384) ? 4 : 3;
-    const size_t lds = sizeof(double) * (size_t)d * ((size_t)1 << tj_shift);  // <= 48 KB
-    hipLaunchKernelGGL(bbh_fps_pairs_generic_kernel, grid, dim3(256), lds, h->stream, a, tj_shift);
-  }
+  bbh_rows_dispatch_dp(d, [&](auto dp) {
+    constexpr int DP = decltype(dp)::value;
+    if constexpr (DP > 0) {
+      hipLaunchKernelGGL(bbh_fps_pairs_kernel<DP>, grid, dim3(256), 0, h->stream, a);
+    } else {
+      const int tj_shift = bbh_rows_tile_shift(d);
+      const size_t lds = sizeof(double) * (size_t)d * ((size_t)1 << tj_shift);  // <= 48 KB
+      hipLaunchKernelGGL(bbh_fps_pairs_generic_kernel, grid, dim3(256), lds, h->stream, a, tj_shift);
+    }
+  });
   BBH_HIP_TRY(h, hipGetLastError());
   hipLaunchKernelGGL(bbh_fps_pairs_final_kernel, dim3(1), dim3(256), 0, h->stream, st->d_key_v, st->d_key_a, st->d_key_b, (int64_t)nkeys,
                      (double*)st->h_small_dev);
@@ -593,7 +558,7 @@ extern "C" int bbh_fps_greedy(bbh_handle* h, const double* P_dev, int64_t M, int
   int rc = fps_small(h, st);
   if (rc) return rc;
   if (n_start > 0) {  // a new selection
-    if ((rc = fps_check_matrix(h, "bbh_fps_greedy", P_dev, M, d, ldp))) return rc;
+    if ((rc = bbh_rows_check(h, "bbh_fps_greedy", P_dev, M, d, ldp, 0))) return rc;  // (the pass loops over any d)
     if (!start_ranks_host || n_start > M) {
       h->err = "bbh_fps_greedy: start ranks missing or more of them than rows";
       return -1;

@@ -26,18 +26,13 @@
 //                               smallest component among equal maxima) and the tile's sum of lpn.
 //   bbh_gmm_bound_kernel        per restart: lower_bound = (the tile sums added in ascending tile order) / N.
 //
-// No floating-point atomics anywhere: every sum has a fixed shape (positions ascending inside a strip, strips ascending, the 64-lane
-// butterfly and the four waves in order, or the MFMA's own order), so two runs give the same bits.  No entry point keeps state: all
-// buffers are the caller's, all launches asynchronous on the handle's stream.
-#include <math.h>
+// No floating-point atomics anywhere: every sum has a fixed shape (positions ascending inside a strip, strips ascending, the block
+// sum of bbh_rows.h, or the MFMA's own order), so two runs give the same bits; nothing is contracted (bbh_rows.h).  No entry point
+// keeps state: all buffers are the caller's, all launches asynchronous on the handle's stream.
+#include "bbh_rows.h"
 
-#include "bbh_common.h"
-
-#pragma clang fp contract(off)
-
-#define GM_TP 256                  // positions per tile
+#define GM_TP BBH_ROWS_TILE        // positions per tile
 #define GM_MAX_D 64                // full covariances: k d^2 doubles, factorised by one workgroup in LDS (64 x 65 doubles = 33 KB)
-#define GM_MAX_ROWS 2147483392ll   // positions are 32-bit inside a tile (2^31 - 256)
 #define GM_MAX_STRIPS 64           // partials per accumulator at the most, whatever M is (k = 100, d = 64: 64 * 100 * 10 * 2 KB = 128 MB)
 #define GM_LDS_BUDGET ((size_t)64 * 1024)
 #define GM_S1_ACC 4                // sweep 1: accumulators per thread
@@ -72,21 +67,6 @@ GmPlan gm_plan(const bbh_handle* h, int d, int64_t k, int64_t M) {
   p.tps = (p.ntiles + GM_MAX_STRIPS - 1) / GM_MAX_STRIPS;
   p.strips = (p.ntiles + p.tps - 1) / p.tps;
   return p;
-}
-
-int gm_check_matrix(bbh_handle* h, const char* who, const double* P_dev, int64_t M, int32_t d, int64_t ldp) {
-  if (!P_dev || M < 1 || M > GM_MAX_ROWS || d < 1 || d > GM_MAX_D || ldp < M) {
-    h->err = std::string(who) + ": bad arguments (need the matrix, 1 <= M < 2^31 - 256, 1 <= d <= 64, ld >= M)";
-    return -1;
-  }
-  return 0;
-}
-
-// the same bits in every lane: a + b == b + a
-__device__ __forceinline__ double gm_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = v + __shfl_xor(v, o, 64);
-  return v;
 }
 
 // r_jc from its source: exp(log_resp [.., k, M]) or the one-hot of labels [.., M] (-1: a row of zeros)
@@ -422,10 +402,8 @@ __global__ __launch_bounds__(256) void bbh_gmm_estep_kernel(const GmEstepArgs A)
     A.labels[dst * A.M + j] = lab;
     if (A.lpn) A.lpn[dst * A.M + j] = lpn;
   }
-  lpn = gm_wave_sum(lpn);
-  if (lane == 0) s_w[wave] = lpn;
-  __syncthreads();
-  if (tid == 0) A.part[tile * A.n_active + slot] = ((s_w[0] + s_w[1]) + s_w[2]) + s_w[3];
+  lpn = bbh_rows_block4_sum(lpn, s_w);
+  if (tid == 0) A.part[tile * A.n_active + slot] = lpn;
 }
 
 // grid (n_active), 64 threads
@@ -440,7 +418,7 @@ __global__ __launch_bounds__(64) void bbh_gmm_bound_kernel(const GmEstepArgs A) 
 // ---- host side ---------------------------------------------------------------------------------------------------------------------
 extern "C" int bbh_gmm_plan(bbh_handle* h, int32_t d, int64_t k, int64_t M, int32_t* comps_per_chunk, int32_t* tiles_per_strip) {
   if (!h) return -1;
-  if (d < 1 || d > GM_MAX_D || k < 1 || M < 1 || M > GM_MAX_ROWS || k > M || !comps_per_chunk || !tiles_per_strip) {
+  if (d < 1 || d > GM_MAX_D || k < 1 || M < 1 || M > BBH_ROWS_MAX || k > M || !comps_per_chunk || !tiles_per_strip) {
     h->err = "bbh_gmm_plan: bad arguments (need 1 <= d <= 64, 1 <= k <= M < 2^31 - 256 and both outputs)";
     return -1;
   }
@@ -454,7 +432,7 @@ extern "C" int bbh_gmm_mstep(bbh_handle* h, const double* P_dev, int64_t M, int3
                              double reg_covar, int32_t normalize, double* work_dev, int64_t work_len, double* nk_dev, double* w_dev,
                              double* mu_dev, double* cov_dev) {
   if (!h) return -1;
-  int rc = gm_check_matrix(h, "bbh_gmm_mstep", P_dev, M, d, ldp);
+  int rc = bbh_rows_check(h, "bbh_gmm_mstep", P_dev, M, d, ldp, GM_MAX_D);
   if (rc) return rc;
   if ((!log_resp_dev) == (!labels_dev) || !rid_dev || !work_dev || !nk_dev || !w_dev || !mu_dev || !cov_dev || k < 1 || k > M || k > 65535 ||
       n_active < 1 || n_active > 65535 || src_base < 0 || !(reg_covar >= 0.0)) {
@@ -509,7 +487,7 @@ extern "C" int bbh_gmm_estep(bbh_handle* h, const double* P_dev, int64_t M, int3
                              int64_t dst_base, double* log_resp_dev, int32_t* labels_dev, double* lpn_dev, double* work_dev,
                              int64_t work_len, double* lower_dev) {
   if (!h) return -1;
-  int rc = gm_check_matrix(h, "bbh_gmm_estep", P_dev, M, d, ldp);
+  int rc = bbh_rows_check(h, "bbh_gmm_estep", P_dev, M, d, ldp, GM_MAX_D);
   if (rc) return rc;
   if (!w_dev || !mu_dev || !prec_dev || !logdet_dev || !rid_dev || !log_resp_dev || !labels_dev || !work_dev || !lower_dev || k < 1 || k > M ||
       n_active < 1 || n_active > 65535 || dst_base < 0) {

@@ -23,20 +23,13 @@
 //   bbh_kmeans_select_kernel       one workgroup per cluster: the member with the smallest sqrt(d2), first on ties; position 0 for a
 //                                  cluster without members.
 //
-// Arithmetic: d2(x, c) = sum_k (x_k - c_k) * (x_k - c_k), k ascending from 0.0, nothing contracted.  No floating-point atomics
-// anywhere: every sum has a fixed shape (inside a tile: one owner in ascending position, or the 64-lane butterfly and the four
-// waves in order; across tiles: ascending), so two runs give the same bits.  No entry point keeps state: all buffers are the
-// caller's, all launches asynchronous on the handle's stream.
-#include <math.h>
+// Arithmetic: the contract of bbh_rows.h (the chains, the wave sums and the key reduction come from there).  Beyond its shapes a
+// sum here is one owner's in ascending position inside a tile and ascending across tiles, so two runs give the same bits.  No entry
+// point keeps state: all buffers are the caller's, all launches asynchronous on the handle's stream.
+#include "bbh_rows.h"
 
-#include "bbh_common.h"
-
-#pragma clang fp contract(off)
-
-#define KM_TP 256                  // positions per tile (one per thread)
+#define KM_TP BBH_ROWS_TILE        // positions per tile (one per thread)
 #define KM_XS 257                  // row stride of the LDS tiles [..][256]: one past the tile, so that rows fall on different banks
-#define KM_MAX_D 768
-#define KM_MAX_ROWS 2147483392ll   // positions are 32-bit inside the kernels (2^31 - 256)
 #define KM_LDS_BUDGET ((size_t)64 * 1024)  // per workgroup: two workgroups share a CU's 160 KB
 #define KM_X_LDS_MAX_D 16          // the tile's own coordinates are staged in LDS up to this width (33 KB), read from L1/L2 beyond
 #define KM_MAX_TRIALS 32           // T = 2 + int(log k) <= 23 for k < 2^31
@@ -75,30 +68,6 @@ KmPlan km_plan(const bbh_handle* h, int d, int64_t k, int64_t R) {
   return p;
 }
 
-int km_check_matrix(bbh_handle* h, const char* who, const double* P_dev, int64_t M, int32_t d, int64_t ldp) {
-  if (!P_dev || M < 1 || M > KM_MAX_ROWS || d < 1 || d > KM_MAX_D || ldp < M) {
-    h->err = std::string(who) + ": bad arguments (need the matrix, 1 <= M < 2^31 - 256, 1 <= d <= 768, ld >= M)";
-    return -1;
-  }
-  return 0;
-}
-
-// the same bits in every lane: a + b == b + a
-__device__ __forceinline__ double km_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = v + __shfl_xor(v, o, 64);
-  return v;
-}
-
-__device__ __forceinline__ double km_d2_to_row(const double* __restrict__ P, int64_t ldp, int d, int64_t j, int64_t i) {
-  double acc = 0.0;
-  for (int k = 0; k < d; k++) {
-    const double t = P[(int64_t)k * ldp + j] - P[(int64_t)k * ldp + i];
-    acc = acc + t * t;
-  }
-  return acc;
-}
-
 __device__ __forceinline__ int64_t km_clamp_row(int64_t i, int64_t M) { return (i < 0) ? 0 : (i >= M) ? M - 1 : i; }
 
 }  // namespace
@@ -116,17 +85,15 @@ __global__ __launch_bounds__(256) void bbh_kmeans_seed_update_kernel(const doubl
   const int64_t i = km_clamp_row(idx[r * k + c], M);
   double v = 0.0;
   if (j < M) {
-    v = km_d2_to_row(P, ldp, d, j, i);
+    v = bbh_rows_d2(P, ldp, d, j, i);
     if (!first) {
       const double old = closest[r * M + j];
       v = (old < v) ? old : v;
     }
     closest[r * M + j] = v;
   }
-  v = km_wave_sum(v);
-  if ((tid & 63) == 0) s_w[tid >> 6] = v;
-  __syncthreads();
-  if (tid == 0) tilesum[r * ntiles + blockIdx.x] = ((s_w[0] + s_w[1]) + s_w[2]) + s_w[3];
+  v = bbh_rows_block4_sum(v, s_w);
+  if (tid == 0) tilesum[r * ntiles + blockIdx.x] = v;
 }
 
 // grid (R), 64 threads; thread t < T searches u[r][(c - 1) T + t] * pot: the first position whose running sum reaches it
@@ -176,14 +143,14 @@ __global__ __launch_bounds__(256) void bbh_kmeans_seed_trial_kernel(const double
   for (int t = 0; t < T; t++) {
     double v = 0.0;
     if (j < M) {
-      v = km_d2_to_row(P, ldp, d, j, km_clamp_row(cand[r * T + t], M));
+      v = bbh_rows_d2(P, ldp, d, j, km_clamp_row(cand[r * T + t], M));
       v = (cl < v) ? cl : v;
     }
-    v = km_wave_sum(v);
+    v = bbh_rows_wave_sum(v);
     if ((tid & 63) == 0) s_w[t][tid >> 6] = v;
   }
   __syncthreads();
-  if (tid < T) trialpart[(r * T + tid) * ntiles + blockIdx.x] = ((s_w[tid][0] + s_w[tid][1]) + s_w[tid][2]) + s_w[tid][3];
+  if (tid < T) trialpart[(r * T + tid) * ntiles + blockIdx.x] = bbh_rows_sum4(s_w[tid]);
 }
 
 // grid (R), 64 threads: idx[r k + c] = the candidate with the smallest trial potential, first on ties
@@ -261,16 +228,9 @@ __global__ __launch_bounds__(256) void bbh_kmeans_pass_kernel(const KmPassArgs A
     }
     __syncthreads();
     for (int qq = 0; qq < nq; qq += 8) {
-      double acc[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-      for (int dim = 0; dim < d; dim++) {
-        const double x = A.x_lds ? s_x[dim * KM_XS + tid] : Pj[(int64_t)dim * A.ldp];
-        const double* cs = s_c + dim * tq + qq;
-#pragma unroll
-        for (int u = 0; u < 8; u++) {
-          const double t = x - cs[u];
-          acc[u] = acc[u] + t * t;
-        }
-      }
+      double acc[8];
+      if (A.x_lds) bbh_rows_d2x8(s_x + tid, KM_XS, s_c + qq, tq, d, acc);
+      else bbh_rows_d2x8(Pj, A.ldp, s_c + qq, tq, d, acc);
 #pragma unroll
       for (int u = 0; u < 8; u++) {
         if (qq + u < nq) {  // (uniform: every thread walks the same centres)
@@ -287,7 +247,7 @@ __global__ __launch_bounds__(256) void bbh_kmeans_pass_kernel(const KmPassArgs A
               v = best;
             }
             s_lab[slot * KM_XS + tid] = live ? lab : -1;
-            v = km_wave_sum(v);
+            v = bbh_rows_wave_sum(v);
             const int any = __any(changed);
             if ((tid & 63) == 0) s_inert[slot * 4 + (tid >> 6)] = v, s_chg[slot * 4 + (tid >> 6)] = any;
             slot++, c = 0, best = INFINITY, lab = 0;
@@ -299,9 +259,8 @@ __global__ __launch_bounds__(256) void bbh_kmeans_pass_kernel(const KmPassArgs A
   __syncthreads();
   const int64_t tile = blockIdx.x;
   if (tid < ns) {
-    const double* w = s_inert + tid * 4;
     const int* g = s_chg + tid * 4;
-    A.part_inert[tile * ns + tid] = ((w[0] + w[1]) + w[2]) + w[3];
+    A.part_inert[tile * ns + tid] = bbh_rows_sum4(s_inert + tid * 4);
     A.part_chg[tile * ns + tid] = g[0] | g[1] | g[2] | g[3];
   }
   if (!A.want_sums) return;
@@ -404,40 +363,22 @@ __global__ __launch_bounds__(256) void bbh_kmeans_finish_kernel(const KmFinishAr
 // grid (k): out[c] = the member of cluster c with the smallest sqrt(d2), the smallest position among equal ones; 0 without members
 __global__ __launch_bounds__(256) void bbh_kmeans_select_kernel(const int* __restrict__ labels, const double* __restrict__ d2, int64_t M,
                                                                 int64_t* __restrict__ out) {
-  __shared__ double s_v[4];
-  __shared__ long long s_p[4];
-  const int tid = threadIdx.x;
+  __shared__ bbh_rows_min_key s_key[4];
   const int c = blockIdx.x;
-  double v = INFINITY;
-  long long vp = -1;
-  for (int64_t j = tid; j < M; j += 256) {
+  bbh_rows_min_key best = {INFINITY, -1};
+  for (int64_t j = threadIdx.x; j < M; j += 256) {
     if (labels[j] != c) continue;
     const double x = __dsqrt_rn(d2[j]);
-    if (vp < 0 || x < v) v = x, vp = j;
+    if (best.p < 0 || x < best.v) best.v = x, best.p = j;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const double ov = __shfl_xor(v, o, 64);
-    const long long op = __shfl_xor(vp, o, 64);
-    if (op >= 0 && (vp < 0 || ov < v || (ov == v && op < vp))) v = ov, vp = op;
-  }
-  if ((tid & 63) == 0) s_v[tid >> 6] = v, s_p[tid >> 6] = vp;
-  __syncthreads();
-  if (tid == 0) {
-    v = s_v[0], vp = s_p[0];
-    for (int w = 1; w < 4; w++) {
-      const double ov = s_v[w];
-      const long long op = s_p[w];
-      if (op >= 0 && (vp < 0 || ov < v || (ov == v && op < vp))) v = ov, vp = op;
-    }
-    out[c] = (vp < 0) ? 0 : vp;  // argmin of an all-infinite column
-  }
+  best = bbh_rows_block_best(best, s_key, bbh_rows_min_beats);
+  if (threadIdx.x == 0) out[c] = (best.p < 0) ? 0 : best.p;  // argmin of an all-infinite column
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------------
 extern "C" int bbh_kmeans_plan(bbh_handle* h, int32_t d, int64_t k, int64_t R, int32_t* restarts_per_tile, int32_t* chunks) {
   if (!h) return -1;
-  if (d < 1 || d > KM_MAX_D || k < 1 || k > KM_MAX_ROWS || R < 1 || !restarts_per_tile || !chunks) {
+  if (d < 1 || d > BBH_ROWS_MAX_D || k < 1 || k > BBH_ROWS_MAX || R < 1 || !restarts_per_tile || !chunks) {
     h->err = "bbh_kmeans_plan: bad arguments (need 1 <= d <= 768, 1 <= k < 2^31 - 256, R >= 1 and both outputs)";
     return -1;
   }
@@ -450,7 +391,7 @@ extern "C" int bbh_kmeans_seed(bbh_handle* h, const double* P_dev, int64_t M, in
                                int64_t R, int64_t k, int32_t T, double* closest_dev, double* tilesum_dev, double* trialpart_dev,
                                int64_t* cand_dev) {
   if (!h) return -1;
-  int rc = km_check_matrix(h, "bbh_kmeans_seed", P_dev, M, d, ldp);
+  int rc = bbh_rows_check(h, "bbh_kmeans_seed", P_dev, M, d, ldp);
   if (rc) return rc;
   if (!idx_dev || !closest_dev || !tilesum_dev || k < 1 || k > M || R < 1 || R > 65535 || T < 1 || T > KM_MAX_TRIALS ||
       (k > 1 && (!U_dev || !trialpart_dev || !cand_dev))) {
@@ -484,7 +425,7 @@ extern "C" int bbh_kmeans_pass(bbh_handle* h, const double* P_dev, int64_t M, in
                                int64_t work_f64_len, int32_t* work_i32_dev, int64_t work_i32_len, double* Cnew_dev, double* sums_dev,
                                int32_t* counts_dev, double* shift_dev, double* inertia_dev, int32_t* flags_dev) {
   if (!h) return -1;
-  int rc = km_check_matrix(h, "bbh_kmeans_pass", P_dev, M, d, ldp);
+  int rc = bbh_rows_check(h, "bbh_kmeans_pass", P_dev, M, d, ldp);
   if (rc) return rc;
   if (!C_dev || !rid_dev || !labels_dev || !d2_dev || !work_f64_dev || !work_i32_dev || !shift_dev || !inertia_dev || !flags_dev ||
       (want_sums && (!Cnew_dev || !sums_dev || !counts_dev)) || k < 1 || k > M || n_active < 1 || n_active > 65535) {
@@ -523,7 +464,7 @@ extern "C" int bbh_kmeans_pass(bbh_handle* h, const double* P_dev, int64_t M, in
 
 extern "C" int bbh_kmeans_select(bbh_handle* h, const int32_t* labels_dev, const double* d2_dev, int64_t M, int64_t k, int64_t* out_dev) {
   if (!h) return -1;
-  if (!labels_dev || !d2_dev || !out_dev || M < 1 || M > KM_MAX_ROWS || k < 1 || k > M) {
+  if (!labels_dev || !d2_dev || !out_dev || M < 1 || M > BBH_ROWS_MAX || k < 1 || k > M) {
     h->err = "bbh_kmeans_select: bad arguments (need the labels, the squared distances, the output, 1 <= M < 2^31 - 256 and "
              "1 <= k <= M)";
     return -1;

@@ -12,6 +12,7 @@ live rows.  Inputs are regenerated from seeds, so the golden file (tests/golden/
             where a workgroup's segment of j grows to two row tiles.
 * grids     product grids, standard-scaled: massive exact ties, held to the oracle's tie rule only.
 * duplicates / identical / single point, and masks with about half the rows dead.
+* edge      the widths of the all-pairs kernels that the generic shapes leave out, held to the oracle only.
 """
 
 from __future__ import annotations
@@ -164,5 +165,20 @@ def mask_cases():
     ]
 
 
+# Every instantiation of the all-pairs walk that the shapes above leave out: d at the upper edge of a register-form width and one
+# past it (so the next width runs with its padding columns), the register form of width 8, and the generic form's 32-, 16- and
+# 8-row tiles (d = 97, 200, 400 and the limit 768).  Held to the oracle only (generic=False: no entry in the golden file).  On
+# these seeds the oracle meets no bit-equal tie, neither in the farthest pair nor in a pick (the largest d2 over all pairs and the
+# largest minimum d2 of every pick each occur once), so no seed needed a shift.
+EDGE_SHAPES = [(130, d) for d in (4, 5, 8, 9, 12, 13, 16, 17, 24, 25, 32)] + [(70, 97), (70, 200), (40, 400), (30, 768)]
+EDGE_MASKED = [(130, 8), (70, 200)]
+
+
+def edge_cases():
+    out = [Case(f"edge-{N}x{d}-farthest-det-n3", _normal(N, d), 3) for N, d in EDGE_SHAPES]
+    out += [Case(f"edge-mask-{N}x{d}-farthest-det-n3", _normal(N, d), 3, alive=_half(N, 20 + d)) for N, d in EDGE_MASKED]
+    return out
+
+
 def all_cases():
-    return generic_cases() + planted_cases() + grid_cases() + degenerate_cases() + mask_cases()
+    return generic_cases() + planted_cases() + grid_cases() + degenerate_cases() + mask_cases() + edge_cases()

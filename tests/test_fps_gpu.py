@@ -87,6 +87,20 @@ def test_grid_scaling_on_the_device_equals_the_host():
     assert np.array_equal(dp.points(), oracle.standard_scale(X)[dp.order])
 
 
+def test_the_greedy_pass_takes_more_columns_than_the_all_pairs_kernels():
+    """768 columns are the limit of the all-pairs kernels' LDS tile alone: an index (or "random") start needs no farthest pair, and
+    the greedy pass loops over any d."""
+    from baybe_amd import sampling
+    from baybe_amd._lib import HipError
+
+    X = np.random.default_rng(769).standard_normal((40, 769))
+    want, want_d2 = oracle.farthest_point_sampling(X, 5, [7, 2], False)
+    idx, d2 = sampling.farthest_point_sampling(X, 5, [7, 2], False, return_distances=True)
+    assert idx == want and np.array_equal(d2, want_d2)
+    with pytest.raises(HipError, match="bbh_fps_farthest_pair: bad arguments.*d <= 768"):
+        sampling.farthest_point_sampling(X, 5, "farthest", False)
+
+
 def test_deterministic_mode_repeats_itself():
     from baybe_amd import sampling
 
