@@ -12,7 +12,8 @@ from baybe_amd._lib import HipError, HipUnavailableError, is_available, library_
 def __getattr__(name):
     """``farthest_point_sampling`` / ``HipFPSRecommender`` (``baybe_amd.sampling``) and ``k_medoids`` / ``HipPAMClusteringRecommender`` /
     ``k_means`` / ``HipKMeansClusteringRecommender`` / ``gaussian_mixture`` / ``HipGaussianMixtureClusteringRecommender``
-    (``baybe_amd.clustering``), imported on first use: the modules pull in pandas and attrs, which a plain ``import baybe_amd`` does
+    (``baybe_amd.clustering``) and ``HipRandomForestSurrogate`` / ``make_baybe_forest_surrogate`` (``baybe_amd.forest``,
+    ``baybe_amd.plugin``), imported on first use: the modules pull in pandas and attrs, which a plain ``import baybe_amd`` does
     not need."""
     if name in ("farthest_point_sampling", "HipFPSRecommender"):
         from baybe_amd import sampling
@@ -23,10 +24,18 @@ def __getattr__(name):
         from baybe_amd import clustering
 
         return getattr(clustering, name)
+    if name in ("HipRandomForestSurrogate", "make_baybe_forest_surrogate"):  # (scikit-learn is imported by the first fit only)
+        if name == "HipRandomForestSurrogate":
+            from baybe_amd import forest
+
+            return forest.HipRandomForestSurrogate
+        from baybe_amd import plugin
+
+        return plugin.make_baybe_forest_surrogate
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 __all__ = ["HipError", "HipUnavailableError", "is_available", "library_path", "farthest_point_sampling", "HipFPSRecommender", "k_medoids",
            "HipPAMClusteringRecommender", "k_means", "HipKMeansClusteringRecommender", "gaussian_mixture",
-           "HipGaussianMixtureClusteringRecommender"]
+           "HipGaussianMixtureClusteringRecommender", "HipRandomForestSurrogate", "make_baybe_forest_surrogate"]
 __version__ = "0.1.0"

@@ -1163,6 +1163,71 @@ class HipGP:
             params["logdet"].data_ptr(), rid.data_ptr(), int(rid.shape[0]), k, base, log_resp.data_ptr(), labels.data_ptr(),
             None if lpn is None else lpn.data_ptr(), work.data_ptr(), work.numel(), params["lower"].data_ptr()), "bbh_gmm_estep")
 
+    # ---- random forest surrogate (baybe_amd.forest) -----------------------------------------------------------------
+    def forest_lds_nodes(self) -> int:
+        """Nodes of the largest tree the kernels walk out of LDS (``bbh_forest_lds_nodes``); larger trees are read from global memory."""
+        return int(self._lib.bbh_forest_lds_nodes())
+
+    def forest_upload(self, packed: dict, d: int) -> dict:
+        """The node tables of a packed forest (``baybe_amd.forest.pack_forest``) on the device, in the layout the ``bbh_forest_*``
+        calls read: ``meta [n, 4]`` int32 (feature, left, right, 0), ``tv [n]`` (threshold of an inner node, value of a leaf),
+        ``off [T + 1]`` int64, and ``order`` = every tree once, ascending."""
+        torch = self._torch()
+        left = np.asarray(packed["children_left"], dtype=np.int32)
+        n, T = len(left), len(packed["offsets"]) - 1
+        meta = np.zeros((n, 4), dtype=np.int32)
+        meta[:, 0], meta[:, 1], meta[:, 2] = packed["feature"], left, packed["children_right"]
+        tv = np.where(left < 0, packed["value"], packed["threshold"]).astype(np.float64)
+        dev = self._dev()
+        return {"meta": torch.from_numpy(meta).to(dev), "tv": torch.from_numpy(tv).to(dev),
+                "off": torch.from_numpy(np.asarray(packed["offsets"], dtype=np.int64).copy()).to(dev),
+                "order": torch.arange(T, dtype=torch.int32, device=dev), "T": T, "n_nodes": n, "d": int(d),
+                "max_nodes": int(np.diff(packed["offsets"]).max())}
+
+    def _forest_args(self, F, X, order, lds_nodes):
+        if X.dim() != 2 or X.shape[1] < F["d"] or X.stride(1) != 1 or X.dtype != self._torch().float64:
+            raise ValueError(f"rows must be fp64 [N, >= {F['d']}] with unit column stride")
+        order = F["order"] if order is None else order
+        lds = self.forest_lds_nodes() if lds_nodes is None else int(lds_nodes)
+        return (X.data_ptr(), int(X.shape[0]), F["d"], int(X.stride(0)), F["meta"].data_ptr(), F["tv"].data_ptr(), F["off"].data_ptr(),
+                F["T"], F["n_nodes"], order.data_ptr(), int(order.shape[0]), lds)
+
+    def forest_predict(self, F, X, lds_nodes=None):
+        """Per-tree predictions ``P [T, N]`` of the device rows ``X`` (``bbh_forest_predict``): for small row sets."""
+        torch = self._torch()
+        P = torch.empty((F["T"], X.shape[0]), dtype=torch.float64, device=X.device)
+        self._check(self._lib.bbh_forest_predict(self._h, *self._forest_args(F, X, None, lds_nodes), P.data_ptr()), "bbh_forest_predict")
+        return P
+
+    def forest_moments(self, F, X, lds_nodes=None):
+        """(mean, unbiased variance) over the trees for the device rows ``X``, ``[N]`` each (``bbh_forest_moments``)."""
+        torch = self._torch()
+        mean = torch.empty(X.shape[0], dtype=torch.float64, device=X.device)
+        var = torch.empty(X.shape[0], dtype=torch.float64, device=X.device)
+        self._check(self._lib.bbh_forest_moments(self._h, *self._forest_args(F, X, None, lds_nodes), mean.data_ptr(), var.data_ptr()),
+                    "bbh_forest_moments")
+        return mean, var
+
+    def forest_mc_acq(self, F, kind: str, X, counts, order, S: int, pend=None, best_f: float = 0.0, sign: float = 1.0,
+                      beta: float = 0.2, alive=None, lds_nodes=None):
+        """MC acquisition values ``[N]`` of the t-batches [x_i ; pending] under the ensemble posterior (``bbh_forest_mc_acq``):
+        ``counts [T]`` int32 samples per tree (``S`` in total), ``order`` int32 = the trees with a count, ascending, ``pend [T, k]``
+        the per-tree predictions of the pending points (None: no pending points)."""
+        torch = self._torch()
+        k = 0 if pend is None else int(pend.shape[1])
+        if counts.shape[0] != F["T"] or counts.dtype != torch.int32 or order.dtype != torch.int32:
+            raise ValueError("counts must be int32 [T] and order int32")
+        if pend is not None and (pend.shape[0] != F["T"] or not pend.is_contiguous() or pend.dtype != torch.float64):
+            raise ValueError("pend must be a contiguous fp64 [T, k] tensor")
+        if alive is not None and (alive.shape[0] != X.shape[0] or alive.dtype != torch.uint8):
+            raise ValueError("alive must be uint8 [N]")
+        scores = torch.empty(X.shape[0], dtype=torch.float64, device=X.device)
+        self._check(self._lib.bbh_forest_mc_acq(
+            self._h, _lib.ACQ_KINDS[kind], *self._forest_args(F, X, order, lds_nodes), counts.data_ptr(), int(S),
+            None if pend is None else pend.data_ptr(), k, float(best_f), float(sign), float(beta),
+            None if alive is None else alive.data_ptr(), scores.data_ptr()), "bbh_forest_mc_acq")
+        return scores
+
     # ---- row-sharded selection through the library's own RCCL communicator ---------------------------------
     def comm_unique_id(self) -> bytes:
         buf = C.create_string_buffer(256)

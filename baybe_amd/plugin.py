@@ -64,6 +64,24 @@ def make_baybe_classes(surrogate_base=None, recommender_base=None, discrete_comp
     return surrogate, composite, recommender
 
 
+def make_baybe_forest_surrogate(surrogate_base=None):
+    """``HipRandomForestSurrogate`` as a subclass of BayBE's ``Surrogate``: the counterpart of ``RandomForestSurrogate``
+    (``baybe/surrogates/random_forest.py:59-144``), built exactly as ``make_baybe_classes`` builds the GP surrogate - the field-less
+    mixin first in the MRO, the base contributing its runtime fields (``_searchspace``, ``_objective``, ``_measurements_hash``).  Use
+    it as ``HipBotorchRecommender(surrogate_model=HipRandomForestSurrogate())``.
+
+    Without an argument the base is imported from ``baybe``; the parameter exists so that the layout can be tested against a replica."""
+    from baybe_amd.forest import HipForestSurrogateImpl, forest_surrogate_fields
+
+    if surrogate_base is None:
+        from baybe.surrogates.base import Surrogate as surrogate_base
+    surrogate = attrs.make_class("HipRandomForestSurrogate", forest_surrogate_fields(with_runtime_state=False),
+                                 bases=(HipForestSurrogateImpl, surrogate_base), slots=True)
+    surrogate.__doc__ = "A random forest surrogate scored on an MI355X (``baybe.surrogates.base.Surrogate``)."
+    surrogate.__module__ = __name__
+    return surrogate
+
+
 def make_baybe_fps_recommender(base=None, discrete_compatibility=None):
     """``HipFPSRecommender`` as a subclass of BayBE's ``NonPredictiveRecommender``
     (``baybe/recommenders/pure/nonpredictive/base.py:17-58``): the counterpart of BayBE's ``FPSRecommender`` for the first,

@@ -221,6 +221,8 @@ class HipRecommenderImpl:
 
     def _setup_acqf(self, searchspace, objective, measurements, pending_experiments=None, acquisition_function=None):
         """Native counterpart of ``_setup_botorch_acqf``: fit (cached), best_f, pending rows."""
+        if getattr(self._surrogate_model, "is_ensemble", False):
+            return self._setup_forest_acqf(searchspace, objective, measurements, pending_experiments, acquisition_function)
         cont = getattr(searchspace, "continuous", None)
         if cont is not None and not getattr(cont, "is_empty", True):
             _check_continuous_part(cont)  # hybrid / continuous spaces: box-bounded continuous parameters only
@@ -282,6 +284,52 @@ class HipRecommenderImpl:
             # _builder.py:141-161, 256-265: the transformed posterior mean at the training inputs
             eng = surrogate.engine
             self._best_f = eng.best_f(surrogate.sign) if self._program is None else eng.best_f(1.0, self._program)
+        return surrogate, acqf
+
+    def _setup_forest_acqf(self, searchspace, objective, measurements, pending_experiments=None, acquisition_function=None):
+        """``_setup_acqf`` for an ensemble surrogate (``baybe_amd.forest.HipRandomForestSurrogate``): what the forest path does not
+        cover is refused before anything is fitted; then the fit (cached), best_f = max_i sign * mean_t P_t(x_i) over the training
+        inputs (_builder.py:141-161), the pending rows, and - for the MC acquisition functions - the forest scorer in the slot of the
+        other device scorers.  Analytic acquisition functions need nothing more: they read the ensemble moments."""
+        from baybe_amd.exceptions import IncompatibleSurrogateError
+        from baybe_amd.forest import HipForestAcq, refuse_continuous
+        from baybe_amd.surrogates import modeled_quantities
+
+        refuse_continuous(searchspace)
+        name = type(self._surrogate_model).__name__
+        if self.shard is not None:
+            raise IncompatibilityError(f"Row shards are not on the HIP path of '{name}'; score the forest on one device.")
+        self._objective = objective
+        acqf = self._get_acquisition_function(objective, acquisition_function)
+        if _is_multi_output(objective) or len(modeled_quantities(objective)) > 1:
+            raise IncompatibleSurrogateError(
+                f"'{name}' is a single-output surrogate; multi-target objectives are not on its HIP path. Use BotorchRecommender."
+            )
+        if acqf.supports_multi_output or getattr(acqf, "kind", None) in ("qNEI", "qLogNEI"):
+            raise IncompatibleAcquisitionFunctionError(
+                f"The acquisition function '{type(acqf).__name__}' is not on the HIP path of '{name}': its ensemble posterior is "
+                f"scored by qLogEI, qEI, qPI, qSR, qUCB, qPSTD and the analytic acquisition functions."
+            )
+        self._program = _check_objective(objective, acqf)
+        if self._program is not None:
+            raise IncompatibilityError(
+                f"Target '{objective.targets[0].name}' carries a transformation; the HIP path of '{name}' supports identity "
+                f"transformations with optional minimisation only."
+            )
+        self._acqf_in_use = acqf
+        if pending_experiments is not None and not acqf.supports_pending_experiments:
+            raise IncompatibleAcquisitionFunctionError(
+                f"The chosen acquisition function of type '{type(acqf).__name__}' does not support pending experiments."
+            )
+        surrogate = self.get_surrogate(searchspace, objective, measurements)
+        self._pending_comp = None
+        if pending_experiments is not None and len(pending_experiments):
+            pend = searchspace.transform(pending_experiments, allow_extra=True)  # _builder.py:326-334
+            self._pending_comp = np.ascontiguousarray(pend.to_numpy(dtype=np.float64))
+        self._best_f = surrogate.engine.best_f(surrogate.sign)
+        self._nehvi = None
+        if not acqf.is_analytic:
+            self._nehvi = HipForestAcq(surrogate, acqf.kind, surrogate.sign, self._best_f, acqf.n_mc_samples, getattr(acqf, "beta", 0.2))
         return surrogate, acqf
 
     def _check_batch_size(self, batch_size, pending_experiments=None) -> None:
@@ -427,6 +475,11 @@ class HipRecommenderImpl:
         surrogate = self._surrogate_model
         acqf = self._acqf_in_use
         Xd, alive, labels = self._candidates_on_device(subspace_discrete, candidates_exp, keep_mask)
+        if self._nehvi is not None and getattr(surrogate, "is_ensemble", False):
+            # the forest scorer: ONE sampler seed per recommendation (an ensemble posterior has no pruning draw)
+            res = self._nehvi.greedy(Xd, batch_size, seed=self._sampler_seed(), X_pending=self._pending_comp, alive=alive)
+            idxs = labels[np.asarray(res.indices, dtype=np.int64)]
+            return (idxs, res) if return_values else idxs
         if self._nehvi is not None:
             res = self._nehvi.greedy(Xd, batch_size, seed=self._sampler_seed(), prune_seed=self._sampler_seed(),
                                      X_pending=self._pending_comp, alive=alive, shard=self.shard)

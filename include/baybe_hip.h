@@ -583,6 +583,39 @@ int bbh_gmm_estep(bbh_handle* h, const double* P_dev, int64_t M, int32_t d, int6
                   const double* prec_dev, const double* logdet_dev, const int32_t* rid_dev, int64_t n_active, int64_t k, int64_t dst_base,
                   double* log_resp_dev, int32_t* labels_dev, double* lpn_dev, double* work_dev, int64_t work_len, double* lower_dev);
 
+/* ---- random forest surrogate: traversal, ensemble moments and the fused MC acquisition pass (bbh_forest.hip) ------------------------
+ * The device side of RandomForestSurrogate (baybe/surrogates/random_forest.py:53-139): the forest is fitted by scikit-learn on the
+ * host; these calls replace the per-tree predictor.predict(candidates), the [T, N] EnsemblePosterior and BoTorch's per-sample gather
+ * from it.  A forest of T trees is meta_dev [n_nodes, 4] int32 (feature, left child, right child, unused; children counted from the
+ * tree's first node, left < 0 marks a leaf), tv_dev [n_nodes] fp64 (threshold of an inner node, value of a leaf) and off_dev [T + 1]
+ * int64 (first node of every tree).  order_dev [n_order] int32 lists the trees a call visits, in the order every row's sums run.  A row
+ * is cast to float32 and goes left iff (double)x32[feature] <= threshold: tree.predict of scikit-learn, bit for bit.  Trees of at most
+ * min(lds_nodes, bbh_forest_lds_nodes()) nodes are walked out of LDS, larger ones in global memory.  A node whose feature or child lies
+ * outside its tree reads as a NaN leaf.  No atomics; a row's result does not depend on where the row sits, so equal rows get equal
+ * bits.  Limits of all: 1 <= N < 2^31 - 256, 1 <= d <= ldx, and 64 float32 rows of d columns must fit into LDS next to the node
+ * tables (d <= 441 with 160 KB).  All are asynchronous on the handle's stream and keep no state. */
+int bbh_forest_lds_nodes(void);
+/* P_dev [T, N]: the prediction of every listed tree for every row (rows of P for trees that are not listed stay untouched).  For small
+ * row sets - training inputs, pending rows, read-backs; the only call that writes a [T, N] array. */
+int bbh_forest_predict(bbh_handle* h, const double* X_dev, int64_t N, int32_t d, int64_t ldx, const int32_t* meta_dev,
+                       const double* tv_dev, const int64_t* off_dev, int64_t T, int64_t n_nodes, const int32_t* order_dev,
+                       int64_t n_order, int32_t lds_nodes, double* P_dev);
+/* EnsemblePosterior.mean / .variance: mean_dev [N] = sum_t P_t / n, var_dev [N] = sum_t (P_t - mean)^2 / (n - 1) over the n listed
+ * trees in their order (two passes), identically 0 for n = 1. */
+int bbh_forest_moments(bbh_handle* h, const double* X_dev, int64_t N, int32_t d, int64_t ldx, const int32_t* meta_dev,
+                       const double* tv_dev, const int64_t* off_dev, int64_t T, int64_t n_nodes, const int32_t* order_dev,
+                       int64_t n_order, int32_t lds_nodes, double* mean_dev, double* var_dev);
+/* MC acquisition values of the t-batches [x_i ; pending] under an ensemble posterior whose sample s reads tree idx_s: counts_dev [T]
+ * int32 = #{s : idx_s = t} (S in total; the listed trees are those with a count > 0), pend_dev [T, k] = P_t of the k <= 63 pending
+ * points.  obj = sign P_t.  BBH_ACQ_QLOGEI: li = log_fatplus(obj - best_f; 1e-6) per point, fatmax over [candidate, pending ...]
+ * (tau 1e-2), score = log sum_t counts[t] exp(v_t - M) + M - log S.  BBH_ACQ_QEI ... BBH_ACQ_QPSTD: bbh_mc_utility per point with m =
+ * the point's count-weighted sample mean, the maximum over the points, the count-weighted mean.  Rows with alive_dev[i] == 0 score
+ * -inf (alive_dev may be null). */
+int bbh_forest_mc_acq(bbh_handle* h, int32_t kind, const double* X_dev, int64_t N, int32_t d, int64_t ldx, const int32_t* meta_dev,
+                      const double* tv_dev, const int64_t* off_dev, int64_t T, int64_t n_nodes, const int32_t* order_dev,
+                      int64_t n_order, int32_t lds_nodes, const int32_t* counts_dev, int64_t S, const double* pend_dev, int64_t k,
+                      double best_f, double sign, double beta, const uint8_t* alive_dev, double* scores_dev);
+
 /* The joint q'-batch and qLogNEHVI kernels split the MC samples into slices when a candidate set alone would not fill the chip; the
  * slice count - and with it the order in which a candidate's partial sums are added - follows the number of candidate rows.
  * rows > 0 fixes the row count the heuristic sees (a row shard passes the GLOBAL count: every rank then adds in the order the
