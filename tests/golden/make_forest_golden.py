@@ -2,6 +2,8 @@
 committed copy was made) under their fixed random_state - per case the packed node arrays, the candidate rows, the training rows and
 scikit-learn's OWN ``estimator.predict`` outputs for both row sets, which is what the device traversal is held to bit for bit on
 machines without scikit-learn.  ``tests/test_forest_cpu.py::test_golden_file_equals_a_fresh_fit`` keeps the file honest.
+Writes tests/golden/forest_mixed.npz as well: the same arrays for ``MIXED``, the forest with trees of 199 to 1399 nodes
+(``tests/test_forest_cpu.py::test_mixed_file_equals_a_fresh_fit``).
 
     python tests/golden/make_forest_golden.py
 """
@@ -33,6 +35,17 @@ def build() -> dict:
     return out
 
 
+def build_mixed() -> dict:
+    estimators, X, train_x, _ = fc.fit_mixed()
+    out = dict(pack_forest(estimators))
+    out["X"], out["train_x"] = X, train_x
+    out["pred"] = np.stack([e.predict(X) for e in estimators])
+    out["pred_train"] = np.stack([e.predict(train_x) for e in estimators])
+    return out
+
+
 if __name__ == "__main__":
     np.savez_compressed(fc.GOLDEN, **build())
     print(fc.GOLDEN, fc.GOLDEN.stat().st_size, "bytes")
+    np.savez_compressed(fc.MIXED_GOLDEN, **build_mixed())
+    print(fc.MIXED_GOLDEN, fc.MIXED_GOLDEN.stat().st_size, "bytes")

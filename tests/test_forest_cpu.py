@@ -1,7 +1,9 @@
 """Host side of the random forest surrogate, and the fixtures the GPU tests stand on: the numpy oracle equals scikit-learn bit for bit,
 the packed layout round-trips, the committed golden file equals a fresh fit, the count-weighted score equals the per-sample one, the
 member draw is reproducible and private, ``model_params`` follows the reference's table, constant targets fall back to one leaf, every
-refusal happens before a fit, and every greedy step of every fixture is decided by a margin the device cannot blur."""
+refusal happens before a fit, and every greedy step of every fixture is decided by a margin the device cannot blur.  The forest of
+production-sized trees (``MIXED``) has its own file: it equals a fresh fit, has the node counts it is for, and its 63-point pending
+blocks leave the candidate its say."""
 
 import functools
 import math
@@ -114,6 +116,46 @@ def test_golden_file_equals_a_fresh_fit():
         assert sorted(z.files) == sorted(fresh)
         for key in z.files:
             assert np.array_equal(z[key], fresh[key]), key
+
+
+@functools.lru_cache(maxsize=None)
+def mixed():
+    return fc.load_mixed()
+
+
+def test_mixed_file_equals_a_fresh_fit():
+    pytest.importorskip("sklearn")
+    import importlib.util
+
+    assert fc.MIXED_GOLDEN.stat().st_size < 100 * 1024
+    spec = importlib.util.spec_from_file_location("make_forest_golden", fc.GOLDEN.parent / "make_forest_golden.py")
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    fresh = mod.build_mixed()
+    with np.load(fc.MIXED_GOLDEN) as z:
+        assert sorted(z.files) == sorted(fresh)
+        for key in z.files:
+            assert np.array_equal(z[key], fresh[key]), key
+
+
+def test_mixed_forest_has_the_sizes_it_is_for_and_the_oracle_walks_it_as_scikit_learn_did():
+    """One tree ending in each 256-node staging slot, one at the 1023-node edge, two above the budget in the 2nd and 4th position, a
+    single leaf last; thresholds exact in float32; ``check_packed`` accepts it; the oracle's walk equals the recorded ``predict``."""
+    from baybe_amd import _lib
+
+    g = mixed()
+    packed = g["packed"]
+    budget = int(_lib.load_library().bbh_forest_lds_nodes())
+    sizes = tuple(int(n) for n in np.diff(packed["offsets"]))
+    assert sizes == fc.MIXED_NODES == (199, 1025, 399, 1399, 659, 1023, 899, 1) and budget == 1024
+    assert sorted({(n - 1) // 256 for n in sizes if 1 < n <= budget}) == [0, 1, 2, 3]
+    assert g["X"].shape == (257, 4) and g["train_x"].shape == (700, 4) and len(np.unique(g["train_x"], axis=0)) == 700
+    assert g["pred"].shape == (8, 257) and g["pred_train"].shape == (8, 700)
+    inner = packed["children_left"] >= 0
+    assert np.array_equal(packed["threshold"][inner].astype(np.float32).astype(np.float64), packed["threshold"][inner])
+    F.check_packed(packed, 4)
+    assert np.array_equal(of.traverse(packed, g["X"]), g["pred"]) and np.array_equal(of.traverse(packed, g["train_x"]), g["pred_train"])
+    assert sorted(g) == ["X", "packed", "pred", "pred_train", "train_x"]
 
 
 def test_over_budget_tree_exceeds_the_exported_budget():
@@ -301,3 +343,39 @@ def test_every_greedy_step_of_every_case_clears_the_margin(name):
             picks, values, margins = of.greedy(kind, P, idx, best, c["sign"], batch, pend)
             assert len(set(picks)) == batch and all(math.isfinite(v) for v in values)
             assert min(margins) >= MARGIN, (name, kind, k, margins)
+
+
+@pytest.mark.parametrize("sign", [1.0, -1.0])
+def test_mixed_pending_block_leaves_the_candidate_its_say(sign):
+    """63 pending points must not swamp the candidate, or the k = 63 scores of the GPU test would be one or two numbers that say
+    nothing about the candidate's walk: under block "a" each of qLogEI, qSR, qUCB and qPSTD takes at least 100 distinct values among
+    the 257 rows at S = 512; block "b" is "a" reversed with the best row in its last slot."""
+    g = mixed()
+    c = fc.MIXED
+    P = g["pred"]
+    idx = F.ensemble_member_indices(512, P.shape[0], c["sampler"])
+    best = of.best_f(g["pred_train"], sign)
+    a, b = fc.mixed_pending_rows(P, sign, "a"), fc.mixed_pending_rows(P, sign, "b")
+    m = sign * of.moments(P)[0]
+    assert len(a) == len(b) == 63 and len(set(a)) == 63 and np.array_equal(b[:-1], a[::-1][:-1]) and b[-1] == np.argmax(m)
+    assert m[a].max() <= np.delete(m, a).min()
+    for kind in ("qLogEI", "qSR", "qUCB", "qPSTD"):
+        distinct = len(np.unique(of.scores(kind, P, P[:, a], idx, best, sign)))
+        assert distinct >= 100, (kind, sign, distinct)
+
+
+def test_every_greedy_step_of_the_mixed_forest_clears_the_margin():
+    """The condition of ``test_every_greedy_step_of_every_case_clears_the_margin`` for the batches the GPU test runs on ``MIXED``."""
+    g = mixed()
+    c = dict(fc.MIXED, **fc.MIXED["greedy"])
+    P = g["pred"]
+    idx = F.ensemble_member_indices(c["S"], P.shape[0], c["sampler"])
+    assert len(set(idx)) == 6 and {1, 3} <= set(idx)  # (both trees above the LDS budget are read)
+    best = of.best_f(g["pred_train"], c["sign"])
+    for kind in fc.MIXED_GREEDY_KINDS:
+        for k in (0, 1):
+            pend = P[:, fc.pending_rows(c["N"], k)] if k else None
+            batch = max(fc.MIXED_BATCHES)
+            picks, values, margins = of.greedy(kind, P, idx, best, c["sign"], batch, pend)
+            assert len(set(picks)) == batch and all(math.isfinite(v) for v in values)
+            assert min(margins) >= MARGIN, (kind, k, margins)

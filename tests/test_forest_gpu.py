@@ -7,6 +7,9 @@ Held to:
   moments, variance                            <= 8 T 2^-53 max|P|^2 absolute, exactly 0 for T = 1
   fused scores, every MC kind, k in {0, 1, 15}, with and without ``alive``: rtol 1e-9, atol 1e-10 (the GP family's bounds)
   duplicated rows: equal bits, first index; two runs: equal bits; greedy batches of 1, 3, 5: the oracle's indices on every case.
+``MIXED`` (trees of 199 to 1399 nodes in one forest) holds the same calls to the same bounds with the LDS / global border at
+{default, 0, 198, 199, 658, 659, 1022, 1023} nodes - equal bits across all of them -, each tree as a pass's first, k = 63 pending points,
+rows read through a stride of 7, and the device's node guard on a table the host check never saw.
 Observed maxima are printed and recorded (conftest.record_deviation)."""
 
 import functools
@@ -422,3 +425,241 @@ def test_constant_targets_recommend_the_first_rows():
     assert list(got.index) == [0, 1, 2] and sur._model is None and sur.engine.n_trees == 1
     mean, var = sur.posterior_mean_var(space.discrete.comp_rep.to_numpy(dtype=np.float64)[:5])
     assert np.array_equal(mean.cpu().numpy(), np.full(5, 1.25)) and np.array_equal(var.cpu().numpy(), np.zeros(5))
+
+
+# ---- trees of the size the kernels were laid out for (MIXED: 199 ... 1399 nodes, LDS and global trees in one pass) ---------------------
+@functools.lru_cache(maxsize=None)
+def mixed():
+    """(fixture, engine) of ``MIXED`` - loaded and uploaded once, never modified."""
+    from baybe_amd.forest import HipForestEngine
+
+    g = fc.load_mixed()
+    eng = HipForestEngine(0)
+    eng._X_train = g["train_x"]
+    eng.set_forest(g["packed"], g["X"].shape[1])
+    assert tuple(int(n) for n in np.diff(g["packed"]["offsets"])) == fc.MIXED_NODES
+    return g, eng
+
+
+def _listed(eng, trees):
+    """The forest of an engine with another list of trees to visit."""
+    import torch
+
+    return dict(eng.forest, order=torch.tensor(list(trees), dtype=torch.int32, device=eng._dev()))
+
+
+@functools.lru_cache(maxsize=None)
+def mixed_draw(S):
+    from baybe_amd.forest import ensemble_member_counts, ensemble_member_indices
+
+    T = len(fc.MIXED_NODES)
+    return ensemble_member_indices(S, T, fc.MIXED["sampler"]), ensemble_member_counts(S, T, fc.MIXED["sampler"])
+
+
+@pytest.mark.parametrize("lds_nodes", fc.MIXED_LDS_NODES)
+def test_mixed_predict_equals_scikit_learn_on_every_path_split(lds_nodes):
+    """The LDS / global border directly below and at 199, 659 and 1023 nodes, all-global and the default: every neighbour pattern of
+    staged and unstaged trees in this order (a global first tree, a staged tree behind a global one and the reverse, the buffer parity
+    carried across trees that were never staged), every staging slot, two row tiles."""
+    g, eng = mixed()
+    for rows, want in ((g["X"], g["pred"]), (g["train_x"][:65], g["pred_train"][:, :65])):
+        got = eng.forest_predict(eng.forest, eng._as_dev(rows), lds_nodes=lds_nodes).cpu().numpy()
+        assert np.array_equal(got, want), (lds_nodes, np.argwhere(got != want)[:8])
+
+
+@pytest.mark.parametrize("lds_nodes", [None, 659])
+def test_mixed_each_tree_as_the_first_tree(lds_nodes):
+    """A pass that lists one tree stages it through the first-tree loop (up to four trips) or walks it in global memory; the reversed
+    and the rotated order put every tree behind another neighbour."""
+    g, eng = mixed()
+    Xd = eng._as_dev(g["X"])
+    for t in range(len(fc.MIXED_NODES)):
+        got = eng.forest_predict(_listed(eng, [t]), Xd, lds_nodes=lds_nodes)[t].cpu().numpy()  # (the other rows are not written)
+        assert np.array_equal(got, g["pred"][t]), (lds_nodes, t)
+    for name, trees in fc.mixed_orders().items():
+        got = eng.forest_predict(_listed(eng, trees), Xd, lds_nodes=lds_nodes).cpu().numpy()
+        assert np.array_equal(got, g["pred"]), (lds_nodes, name)
+
+
+def test_mixed_moments_within_the_summation_bounds_on_every_path_split():
+    g, eng = mixed()
+    P = g["pred"]
+    Xd = eng._as_dev(g["X"])
+    T, big = P.shape[0], np.abs(P).max()
+    worst = [0.0, 0.0]
+    for name, trees in fc.mixed_orders().items():
+        mo, vo = of.moments(P[trees])
+        F = _listed(eng, trees)
+        first = None
+        for lds_nodes in fc.MIXED_LDS_NODES:
+            mean, var = (v.cpu().numpy() for v in eng.forest_moments(F, Xd, lds_nodes=lds_nodes))
+            worst = [max(worst[0], np.abs(mean - mo).max()), max(worst[1], np.abs(var - vo).max())]
+            if first is None:
+                first = (mean, var)
+            assert np.array_equal(mean, first[0]) and np.array_equal(var, first[1]), (name, lds_nodes, "differs from the default path")
+    print(f"forest moments MIXED: mean dev {worst[0]:.3e} (bound {2 * T * EPS * big:.3e}), var dev {worst[1]:.3e} "
+          f"(bound {8 * T * EPS * big * big:.3e})")
+    record_deviation("forest_moments_mean[mixed]", worst[0], 2 * T * EPS * big)
+    record_deviation("forest_moments_var[mixed]", worst[1], 8 * T * EPS * big * big)
+    assert worst[0] <= 2 * T * EPS * big
+    assert worst[1] <= 8 * T * EPS * big * big
+    for lds_nodes in (None, 659):
+        for t in range(T):
+            mean, var = (v.cpu().numpy() for v in eng.forest_moments(_listed(eng, [t]), Xd, lds_nodes=lds_nodes))
+            assert np.array_equal(var, np.zeros_like(var)) and np.array_equal(mean, P[t]), (lds_nodes, t)
+
+
+@pytest.mark.parametrize("sign", [1.0, -1.0])
+@pytest.mark.parametrize("kind", fc.MC_KINDS)
+def test_mixed_fused_scores_with_63_pending_points(kind, sign):
+    """k = 0 and the two k = 63 blocks (the last slot of the pending block in use), S = 5 (fewer samples than trees: some are skipped)
+    and 512, against the per-sample oracle; the same bits on every path split; the oracle's winner masked."""
+    import torch
+
+    g, eng = mixed()
+    P, X = g["pred"], g["X"]
+    Xd = eng._as_dev(X)
+    dev = eng._dev()
+    best = of.best_f(g["pred_train"], sign)
+    worst = 0.0
+    for S in fc.MIXED_SAMPLES:
+        idx, counts = mixed_draw(S)
+        counts_d = torch.from_numpy(counts).to(dev)
+        order = torch.from_numpy(np.nonzero(counts)[0].astype(np.int32)).to(dev)
+        for block in (None, "a", "b"):
+            pend = None if block is None else np.ascontiguousarray(P[:, fc.mixed_pending_rows(P, sign, block)])
+            pend_d = None if pend is None else torch.from_numpy(pend).to(dev)
+            assert (0 if pend is None else pend.shape[1]) in fc.MIXED_PENDING
+            want = of.scores(kind, P, pend, idx, best, sign)
+            first = None
+            for lds_nodes in fc.MIXED_LDS_NODES:
+                got = eng.forest_mc_acq(eng.forest, kind, Xd, counts_d, order, S, pend_d, best, sign, lds_nodes=lds_nodes).cpu().numpy()
+                if first is None:
+                    first = got
+                    assert np.allclose(got, want, rtol=1e-9, atol=1e-10), (kind, sign, S, block, np.abs(got - want).max())
+                    worst = max(worst, float((np.abs(got - want) / (1e-10 + 1e-9 * np.abs(want))).max()))
+                assert np.array_equal(got, first), (kind, sign, S, block, lds_nodes, "differs from the default path")
+            alive = np.ones(len(X), dtype=np.uint8)
+            alive[int(np.argmax(want))] = 0
+            m = eng.forest_mc_acq(eng.forest, kind, Xd, counts_d, order, S, pend_d, best, sign,
+                                  alive=torch.from_numpy(alive).to(dev)).cpu().numpy()
+            live = alive.astype(bool)
+            assert np.all(np.isneginf(m[~live])) and np.array_equal(m[live], first[live])
+            if S == 512 and block == "b":  # a pass that starts at the 1399-node tree: other summation order, same allowance
+                rot = torch.tensor(fc.mixed_orders()["rotated"], dtype=torch.int32, device=dev)
+                got = eng.forest_mc_acq(eng.forest, kind, Xd, counts_d, rot, S, pend_d, best, sign).cpu().numpy()
+                assert np.allclose(got, want, rtol=1e-9, atol=1e-10), (kind, sign, "rotated", np.abs(got - want).max())
+                worst = max(worst, float((np.abs(got - want) / (1e-10 + 1e-9 * np.abs(want))).max()))
+    print(f"forest fused scores MIXED {kind} sign {sign:+.0f}: worst deviation = {worst:.3e} of the allowance")
+    record_deviation(f"forest_fused_scores_share_of_allowance[mixed-{kind}-{'max' if sign > 0 else 'min'}]", worst, 1.0)
+
+
+def test_64_pending_points_are_refused():
+    """One more than the pending slot holds: refused on the host, nothing is launched."""
+    import torch
+
+    from baybe_amd.engine import HipError
+
+    g, eng = mixed()
+    _, counts = mixed_draw(512)
+    dev = eng._dev()
+    pend = torch.zeros((len(fc.MIXED_NODES), 64), dtype=torch.float64, device=dev)
+    with pytest.raises(HipError, match="63"):
+        eng.forest_mc_acq(eng.forest, "qLogEI", eng._as_dev(g["X"]), torch.from_numpy(counts).to(dev), eng.forest["order"], 512, pend)
+
+
+def test_mixed_strided_rows_give_the_bits_of_contiguous_rows():
+    """Rows inside a wider matrix (row stride 7, every other row off the 16-byte grid) and with columns behind the d the forest reads:
+    the surroundings hold 1e30, so a column or row taken from them changes a walk."""
+    import torch
+
+    g, eng = mixed()
+    P, X = g["pred"], g["X"]
+    dev = eng._dev()
+    Xd = eng._as_dev(X)
+    idx, counts = mixed_draw(512)
+    counts_d = torch.from_numpy(counts).to(dev)
+    pend_d = torch.from_numpy(np.ascontiguousarray(P[:, fc.mixed_pending_rows(P, 1.0, "a")])).to(dev)
+    best = of.best_f(g["pred_train"], 1.0)
+
+    def results(rows):
+        mean, var = eng.forest_moments(eng.forest, rows)
+        return (eng.forest_predict(eng.forest, rows), mean, var,
+                eng.forest_mc_acq(eng.forest, "qLogEI", rows, counts_d, eng.forest["order"], 512, pend_d, best, 1.0))
+
+    ref = results(Xd)
+    assert np.array_equal(ref[0].cpu().numpy(), P)
+    W = torch.full((260, 7), 1e30, dtype=torch.float64, device=dev)
+    W[3:, 1:5] = Xd
+    W2 = torch.full((260, 7), 1e30, dtype=torch.float64, device=dev)  # the same rows, the first element off the 16-byte grid too
+    W2[2:259, 1:5] = Xd
+    assert W2[2:259, 1:5].data_ptr() % 16 == 8
+    for view in (W[3:, 1:5], W[3:, 1:], W2[2:259, 1:5], W2[2:259, 1:]):
+        assert view.stride(0) == 7 and view.shape[1] in (4, 6) and not view.is_contiguous()
+        for got, want in zip(results(view), ref):
+            assert torch.equal(got, want)
+    for view in (W[3:4, 1:5], W2[2:3, 1:5]):
+        assert view.shape == (1, 4)
+        p, mean, var, score = results(view)
+        assert torch.equal(p, ref[0][:, :1]) and torch.equal(mean, ref[1][:1]) and torch.equal(var, ref[2][:1])
+        assert torch.equal(score, ref[3][:1])
+
+
+def test_mixed_greedy_batches_return_the_oracles_indices():
+    """Nothing is skipped: every step clears 1e-8 in the oracle
+    (tests/test_forest_cpu.py::test_every_greedy_step_of_the_mixed_forest_clears_the_margin)."""
+    from baybe_amd.forest import HipForestAcq
+
+    from baybe_amd.forest import ensemble_member_indices
+
+    g, eng = mixed()
+    c = dict(fc.MIXED, **fc.MIXED["greedy"])
+    P, X = g["pred"], g["X"]
+    Xd = eng._as_dev(X)
+    idx = ensemble_member_indices(c["S"], P.shape[0], c["sampler"])
+    best = of.best_f(g["pred_train"], c["sign"])
+    for kind in fc.MIXED_GREEDY_KINDS:
+        acq = HipForestAcq(_Holder(eng), kind, c["sign"], best, c["S"])
+        for k in (0, 1):
+            rows = fc.pending_rows(c["N"], k)
+            for batch in fc.MIXED_BATCHES:
+                want, values, _ = of.greedy(kind, P, idx, best, c["sign"], batch, P[:, rows] if k else None)
+                res = acq.greedy(Xd, batch, seed=c["sampler"], X_pending=X[rows] if k else None)
+                assert res.indices == want, (kind, k, batch, res.indices, want)
+                assert np.allclose(res.values, values, rtol=1e-9, atol=1e-10)
+
+
+@pytest.mark.parametrize("lds_nodes", [None, 0])
+def test_a_node_pointing_outside_its_tree_becomes_a_nan_leaf(lds_nodes):
+    """The device guard (``check_packed`` refuses such tables on the host; ``forest_upload`` does not look): an inner node of the
+    659-node tree, in the third staging slot, gets a child equal to the tree's node count - the next tree's first node in global
+    memory, an unstaged entry of the LDS table - and, separately, the feature d = 4 - the padding column of the LDS row.  Neither
+    leaves an allocation.  Rows whose walk reaches the node get NaN from that tree; everything else keeps scikit-learn's bits."""
+    g, eng = mixed()
+    packed, d, t = g["packed"], g["X"].shape[1], 4
+    off = packed["offsets"]
+    first, nn = int(off[t]), int(off[t + 1] - off[t])
+    assert nn == 659 and t + 1 < len(fc.MIXED_NODES)
+    rows = np.concatenate([g["X"], g["train_x"]])
+    recorded = np.concatenate([g["pred"], g["pred_train"]], axis=1)
+    tree = {k: packed[k][first:first + nn] for k in fc.PACKED_KEYS if k != "offsets"}
+    tree["offsets"] = np.array([0, nn], dtype=np.int64)
+
+    def reached(node):  # the oracle's walk on the unaltered tree, cut at the node
+        cut = {k: v.copy() for k, v in tree.items()}
+        cut["children_left"][node] = cut["children_right"][node] = -1
+        cut["value"][node] = np.nan
+        return np.isnan(of.traverse(cut, rows)[0])
+
+    inner = [n for n in range(512, nn) if tree["children_left"][n] >= 0]
+    hit = {n: reached(n) for n in inner}
+    node = max(inner, key=lambda n: int(hit[n].sum()))
+    assert 2 <= hit[node].sum() < len(rows)
+    want = recorded.copy()
+    want[t, hit[node]] = np.nan
+    Xd = eng._as_dev(rows)
+    for key, value in (("children_left", nn), ("children_right", nn), ("feature", d)):
+        bad = {k: v.copy() for k, v in packed.items()}
+        bad[key][first + node] = value
+        got = eng.forest_predict(eng.forest_upload(bad, d), Xd, lds_nodes=lds_nodes).cpu().numpy()
+        assert np.array_equal(got, want, equal_nan=True), (key, lds_nodes)
