@@ -13,6 +13,7 @@ def __getattr__(name):
     """``farthest_point_sampling`` / ``HipFPSRecommender`` (``baybe_amd.sampling``) and ``k_medoids`` / ``HipPAMClusteringRecommender`` /
     ``k_means`` / ``HipKMeansClusteringRecommender`` / ``gaussian_mixture`` / ``HipGaussianMixtureClusteringRecommender``
     (``baybe_amd.clustering``) and ``HipRandomForestSurrogate`` / ``make_baybe_forest_surrogate`` (``baybe_amd.forest``,
+    ``baybe_amd.plugin``) and ``HipBayesianLinearSurrogate`` / ``make_baybe_linear_surrogate`` (``baybe_amd.linear``,
     ``baybe_amd.plugin``), imported on first use: the modules pull in pandas and attrs, which a plain ``import baybe_amd`` does
     not need."""
     if name in ("farthest_point_sampling", "HipFPSRecommender"):
@@ -32,10 +33,19 @@ def __getattr__(name):
         from baybe_amd import plugin
 
         return plugin.make_baybe_forest_surrogate
+    if name == "HipBayesianLinearSurrogate":  # (scikit-learn is imported by the first fit only)
+        from baybe_amd import linear
+
+        return linear.HipBayesianLinearSurrogate
+    if name == "make_baybe_linear_surrogate":
+        from baybe_amd import plugin
+
+        return plugin.make_baybe_linear_surrogate
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 __all__ = ["HipError", "HipUnavailableError", "is_available", "library_path", "farthest_point_sampling", "HipFPSRecommender", "k_medoids",
            "HipPAMClusteringRecommender", "k_means", "HipKMeansClusteringRecommender", "gaussian_mixture",
-           "HipGaussianMixtureClusteringRecommender", "HipRandomForestSurrogate", "make_baybe_forest_surrogate"]
+           "HipGaussianMixtureClusteringRecommender", "HipRandomForestSurrogate", "make_baybe_forest_surrogate",
+           "HipBayesianLinearSurrogate", "make_baybe_linear_surrogate"]
 __version__ = "0.1.0"

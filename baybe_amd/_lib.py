@@ -237,6 +237,9 @@ SIGNATURES = {
     "bbh_forest_mc_acq": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                     C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
+    "bbh_linear_moments": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                     C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_void_p, C.c_void_p]),
+    "bbh_linear_last_form": (C.c_int, [C.c_void_p]),
     "bbh_comm_unique_id": (C.c_int, [C.c_void_p, C.c_int64]),
     "bbh_comm_init": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64]),
     "bbh_comm_destroy": (C.c_int, [C.c_void_p]),

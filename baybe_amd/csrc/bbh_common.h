@@ -352,6 +352,7 @@ struct bbh_handle {
   int last_form = -1;             // bbh_last_posterior_form
   int last_fit_form = -1;         // bbh_last_fit_form (enum bbh_fit_form)
   int last_nei_form = -1;         // bbh_last_nei_form: 1 fused (bbh_score_nei), 2 unfused (bbh_nei_q1)
+  int last_linear_form = -1;      // bbh_linear_last_form: 1 register, 2 block (bbh_linear_moments)
   int64_t nb_ext = 0;             // blocks incl. pending points (mean/cross pass)
   // pending state
   int p = 0;

@@ -1228,6 +1228,40 @@ class HipGP:
             None if alive is None else alive.data_ptr(), scores.data_ptr()), "bbh_forest_mc_acq")
         return scores
 
+    # ---- Bayesian linear surrogate (baybe_amd.linear) ----------------------------------------------------------------
+    def linear_upload(self, packed: dict) -> dict:
+        """The tables of a packed linear model (``baybe_amd.linear.pack_linear``) on the device, in the layout ``bbh_linear_moments``
+        reads: ``cols [k]`` int32, ``scale [3, k]`` (lo, range, coef) and ``T [k, k]``."""
+        torch = self._torch()
+        dev = self._dev()
+        k = int(len(packed["cols"]))
+        scale = np.ascontiguousarray(np.stack([packed["lo"], packed["range"], packed["coef"]]).astype(np.float64)).reshape(3, k)
+        return {"cols": torch.from_numpy(np.ascontiguousarray(packed["cols"], dtype=np.int32)).to(dev),
+                "scale": torch.from_numpy(scale).to(dev),
+                "T": torch.from_numpy(np.ascontiguousarray(packed["T"], dtype=np.float64).reshape(k, k)).to(dev), "k": k,
+                "intercept": float(packed["intercept"]), "inv_alpha": float(packed["inv_alpha"])}
+
+    def linear_moments(self, L, X, ybar: float = 0.0, ysd: float = 1.0, form="auto"):
+        """(mean, variance) ``[N]`` of the device rows ``X`` under the uploaded linear model ``L`` (``bbh_linear_moments``);
+        ``form``: "auto" (by the number of kept columns), "register" or "block"."""
+        torch = self._torch()
+        if X.dim() != 2 or X.stride(1) != 1 or X.dtype != torch.float64:
+            raise ValueError("rows must be fp64 [N, d] with unit column stride")
+        N, k = int(X.shape[0]), L["k"]
+        mean = torch.empty(N, dtype=torch.float64, device=X.device)
+        var = torch.empty(N, dtype=torch.float64, device=X.device)
+        ptr = (lambda t: t.data_ptr()) if k else (lambda t: None)
+        self._check(self._lib.bbh_linear_moments(
+            self._h, X.data_ptr() if N else None, N, int(X.shape[1]), int(X.stride(0)) if N > 1 else max(int(X.stride(0)), int(X.shape[1])),
+            ptr(L["cols"]), ptr(L["scale"]), ptr(L["T"]), k, L["intercept"], L["inv_alpha"], float(ybar), float(ysd),
+            form if isinstance(form, int) else {"auto": 0, "register": 1, "block": 2}[form], mean.data_ptr(), var.data_ptr()),
+            "bbh_linear_moments")
+        return mean, var
+
+    def linear_last_form(self) -> str:
+        """Form the last ``linear_moments`` of this handle ran as (``bbh_linear_last_form``)."""
+        return {1: "register", 2: "block"}.get(self._lib.bbh_linear_last_form(self._h), "none")
+
     # ---- row-sharded selection through the library's own RCCL communicator ---------------------------------
     def comm_unique_id(self) -> bytes:
         buf = C.create_string_buffer(256)

@@ -82,6 +82,23 @@ def make_baybe_forest_surrogate(surrogate_base=None):
     return surrogate
 
 
+def make_baybe_linear_surrogate(surrogate_base=None):
+    """``HipBayesianLinearSurrogate`` as a subclass of BayBE's ``Surrogate``: the counterpart of ``BayesianLinearSurrogate``
+    (``baybe/surrogates/linear.py:39-94``), built as ``make_baybe_forest_surrogate`` builds the forest - the field-less mixin first in
+    the MRO, the base contributing its runtime fields.  Use it as ``HipBotorchRecommender(surrogate_model=HipBayesianLinearSurrogate())``.
+
+    Without an argument the base is imported from ``baybe``; the parameter exists so that the layout can be tested against a replica."""
+    from baybe_amd.linear import HipLinearSurrogateImpl, linear_surrogate_fields
+
+    if surrogate_base is None:
+        from baybe.surrogates.base import Surrogate as surrogate_base
+    surrogate = attrs.make_class("HipBayesianLinearSurrogate", linear_surrogate_fields(with_runtime_state=False),
+                                 bases=(HipLinearSurrogateImpl, surrogate_base), slots=True)
+    surrogate.__doc__ = "A Bayesian linear (ARD) surrogate scored on an MI355X (``baybe.surrogates.base.Surrogate``)."
+    surrogate.__module__ = __name__
+    return surrogate
+
+
 def make_baybe_fps_recommender(base=None, discrete_compatibility=None):
     """``HipFPSRecommender`` as a subclass of BayBE's ``NonPredictiveRecommender``
     (``baybe/recommenders/pure/nonpredictive/base.py:17-58``): the counterpart of BayBE's ``FPSRecommender`` for the first,

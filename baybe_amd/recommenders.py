@@ -223,6 +223,8 @@ class HipRecommenderImpl:
         """Native counterpart of ``_setup_botorch_acqf``: fit (cached), best_f, pending rows."""
         if getattr(self._surrogate_model, "is_ensemble", False):
             return self._setup_forest_acqf(searchspace, objective, measurements, pending_experiments, acquisition_function)
+        if getattr(self._surrogate_model, "is_independent_gaussian", False):
+            return self._setup_linear_acqf(searchspace, objective, measurements, pending_experiments, acquisition_function)
         cont = getattr(searchspace, "continuous", None)
         if cont is not None and not getattr(cont, "is_empty", True):
             _check_continuous_part(cont)  # hybrid / continuous spaces: box-bounded continuous parameters only
@@ -332,12 +334,61 @@ class HipRecommenderImpl:
             self._nehvi = HipForestAcq(surrogate, acqf.kind, surrogate.sign, self._best_f, acqf.n_mc_samples, getattr(acqf, "beta", 0.2))
         return surrogate, acqf
 
+    def _setup_linear_acqf(self, searchspace, objective, measurements, pending_experiments=None, acquisition_function=None):
+        """``_setup_acqf`` for an independent-Gaussian surrogate (``baybe_amd.linear.HipBayesianLinearSurrogate``): what its path does
+        not cover is refused before anything is fitted; then the fit (cached), best_f = max_i objective(mean at training row i)
+        (_builder.py:141-161), and - for the MC acquisition functions - the q = 1 scorer in the slot of the other device scorers.
+        Analytic acquisition functions need nothing more: they read the moments.  A transformed single target rides on the objective
+        program, as on the GP path."""
+        from baybe_amd.exceptions import IncompatibleSurrogateError
+        from baybe_amd.forest import refuse_continuous
+        from baybe_amd.linear import JOINT_TEXT, HipLinearAcq, refuse_task_parameters
+        from baybe_amd.surrogates import modeled_quantities
+
+        name = type(self._surrogate_model).__name__
+        refuse_task_parameters(searchspace, name)
+        refuse_continuous(searchspace)
+        self._objective = objective
+        acqf = self._get_acquisition_function(objective, acquisition_function)
+        if _is_multi_output(objective) or len(modeled_quantities(objective)) > 1:
+            raise IncompatibleSurrogateError(
+                f"'{name}' is a single-output surrogate; multi-target objectives are not on its HIP path. Use BotorchRecommender."
+            )
+        if acqf.supports_multi_output or getattr(acqf, "kind", None) in ("qNEI", "qLogNEI"):
+            raise IncompatibleAcquisitionFunctionError(
+                f"The acquisition function '{type(acqf).__name__}' is not on the HIP path of '{name}': its independent Gaussian "
+                f"posterior is scored by qLogEI, qEI, qPI, qSR, qUCB, qPSTD and the analytic acquisition functions."
+            )
+        if pending_experiments is not None and len(pending_experiments):
+            raise IncompatibleSurrogateError(f"'{name}' {JOINT_TEXT}.")
+        if self.shard is not None:
+            raise IncompatibilityError(f"Row shards are not on the HIP path of '{name}'; score the linear model on one device.")
+        self._program = _check_objective(objective, acqf)
+        self._acqf_in_use = acqf
+        surrogate = self.get_surrogate(searchspace, objective, measurements)
+        self._pending_comp = None
+        eng = surrogate.engine
+        self._best_f = eng.best_f(surrogate.sign) if self._program is None else eng.best_f(1.0, self._program)
+        self._nehvi = None
+        if not acqf.is_analytic:
+            self._nehvi = HipLinearAcq(surrogate, acqf.kind, self._sign(surrogate), self._best_f, acqf.n_mc_samples,
+                                       getattr(acqf, "beta", 0.2), self._program)
+        return surrogate, acqf
+
     def _check_batch_size(self, batch_size, pending_experiments=None) -> None:
         """The joint q'-batch kernels hold 1 + (pending + earlier picks) <= 16 points; the reference has no such
         limit, so say so before any candidate is scored (single-target MC acquisition functions only: qLogNEHVI and
         qNEI / qLogNEI cache picks into their baseline and analytic functions have q = 1)."""
         n_pend = len(self._pending_comp) if self._pending_comp is not None else (
             0 if pending_experiments is None else len(pending_experiments))
+        if getattr(self._surrogate_model, "is_independent_gaussian", False):
+            # an independent Gaussian per point has no joint posterior (surrogates/base.py:484-503): one point, nothing pending
+            if batch_size > 1 or n_pend > 0:
+                from baybe_amd.exceptions import IncompatibleSurrogateError
+                from baybe_amd.linear import JOINT_TEXT
+
+                raise IncompatibleSurrogateError(f"'{type(self._surrogate_model).__name__}' {JOINT_TEXT}.")
+            return
         acqf = self._acqf_in_use
         if acqf is not None and (acqf.supports_multi_output or getattr(acqf, "is_analytic", False)
                                  or getattr(acqf, "kind", None) in ("qNEI", "qLogNEI")):
@@ -475,8 +526,8 @@ class HipRecommenderImpl:
         surrogate = self._surrogate_model
         acqf = self._acqf_in_use
         Xd, alive, labels = self._candidates_on_device(subspace_discrete, candidates_exp, keep_mask)
-        if self._nehvi is not None and getattr(surrogate, "is_ensemble", False):
-            # the forest scorer: ONE sampler seed per recommendation (an ensemble posterior has no pruning draw)
+        if self._nehvi is not None and (getattr(surrogate, "is_ensemble", False) or getattr(surrogate, "is_independent_gaussian", False)):
+            # the forest / linear scorer: ONE sampler seed per recommendation (their posteriors have no pruning draw)
             res = self._nehvi.greedy(Xd, batch_size, seed=self._sampler_seed(), X_pending=self._pending_comp, alive=alive)
             idxs = labels[np.asarray(res.indices, dtype=np.int64)]
             return (idxs, res) if return_values else idxs
@@ -677,6 +728,11 @@ class HipRecommenderImpl:
     # ---- read-backs (Campaign.acquisition_values / joint_acquisition_value) ---------------------
     def _joint_value(self, comp: np.ndarray) -> float:
         """qLogEI of one q-batch (candidate = first row, the others enter as pending rows)."""
+        if getattr(self._surrogate_model, "is_independent_gaussian", False) and len(comp) != 1:
+            from baybe_amd.exceptions import IncompatibleSurrogateError
+            from baybe_amd.linear import JOINT_TEXT
+
+            raise IncompatibleSurrogateError(f"'{type(self._surrogate_model).__name__}' {JOINT_TEXT}.")
         if self._nehvi is not None:
             # incremental NEHVI: the batch value is the value of its last point given the others
             self._nehvi.prepare(self._sampler_seed(), np.vstack([comp[:-1]] + ([self._pending_comp] if self._pending_comp is not None else [])) if len(comp) > 1 or self._pending_comp is not None else None)

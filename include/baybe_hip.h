@@ -616,6 +616,26 @@ int bbh_forest_mc_acq(bbh_handle* h, int32_t kind, const double* X_dev, int64_t 
                       int64_t n_order, int32_t lds_nodes, const int32_t* counts_dev, int64_t S, const double* pend_dev, int64_t k,
                       double best_f, double sign, double beta, const uint8_t* alive_dev, double* scores_dev);
 
+/* ---- Bayesian linear (ARD) surrogate: predictive moments of every row in one pass (bbh_linear.hip) -------------------------------------
+ * The device side of BayesianLinearSurrogate (baybe/surrogates/linear.py:62-82): ARDRegression is fitted by scikit-learn on the host;
+ * this call replaces model.predict(X, return_std=True) over the candidates.  Of the k <= 512 kept columns (lambda_ < threshold_lambda)
+ * cols_dev [k] int32 holds the column of the rows, scale_dev [3, k] the lower bound, the range hi - lo (> 0) and coef_, and T_dev
+ * [k, k] the matrix T[i][i] = Ss[i][i], T[i][j] = 2 Ss[i][j] (j < i), 0 above the diagonal, Ss = (sigma_ + sigma_^T) / 2 (entries above
+ * the diagonal are not read).  With x~_j = (x[cols_j] - lo_j) / range_j:
+ *   mean_dev[i] = ybar + ysd * (sum_j x~_j coef_j + intercept),  var_dev[i] = ysd^2 * (sum_i x~_i sum_{j <= i} T[i][j] x~_j + inv_alpha).
+ * form: 0 = by size (register form for k <= 16, block form above: the measured crossover), 1 = register form (one thread per row,
+ * k <= 32), 2 = block form
+ * (16 rows per wave on v_mfma_f64_16x16x4_f64, any k >= 1).  k = 0 fills the two constants in either form.  Every sum has a fixed
+ * order and nothing is contracted: equal rows get equal bits within a form.  Stateless apart from the form of the last call; the
+ * launch is asynchronous on the handle's stream after the column list has been read back and checked.  N == 0 is a no-op.  Returns -1
+ * with an error text for k < 0, k > 512, form 1 with k > 32, a column index outside [0, d), ldx < d, or a null pointer where one is
+ * needed (the outputs; for k > 0 the rows and the tables). */
+int bbh_linear_moments(bbh_handle* h, const double* X_dev, int64_t N, int32_t d, int64_t ldx, const int32_t* cols_dev,
+                       const double* scale_dev, const double* T_dev, int32_t k, double intercept, double inv_alpha, double ybar, double ysd,
+                       int32_t form, double* mean_dev, double* var_dev);
+/* Form the last bbh_linear_moments of this handle ran as: 1 = register, 2 = block, -1 = none yet. */
+int bbh_linear_last_form(bbh_handle* h);
+
 /* The joint q'-batch and qLogNEHVI kernels split the MC samples into slices when a candidate set alone would not fill the chip; the
  * slice count - and with it the order in which a candidate's partial sums are added - follows the number of candidate rows.
  * rows > 0 fixes the row count the heuristic sees (a row shard passes the GLOBAL count: every rank then adds in the order the
