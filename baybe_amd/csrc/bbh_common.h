@@ -346,7 +346,7 @@ struct bbh_handle {
   int64_t rstream_frags = 0;
   int coop_g0 = 0;
   int coop_kds = 0;               // k-steps of the seeded distance GEMM of the cooperative form; 0: the augmented stream is used
-  double* d_trainfrag_s = nullptr;  // [nb][coop_kds][64] training fragments without augmentation rows, scaled by sqrt(5) | [16 nb] squared norms
+  double* d_trainfrag_s = nullptr;  // [nb][coop_kds][64] training fragments without augmentation rows, scaled by sqrt(5), k-steps in lane-interleaved pairs | [16 nb] alpha | [16 nb] squared norms
   int64_t tf_s_elems = 0;
   int last_seeded = 0;            // the last cooperative launch (last_form == 1) was the seeded one: bbh_last_posterior_seeded
   int last_form = -1;             // bbh_last_posterior_form

@@ -13,8 +13,13 @@
 //             balances the triangular work exactly: 528 variance MFMAs per wave at n = 512.
 //   k-blocks  in groups of four (group g = round g).  While a wave consumes group g (its slots rho >= g; the diagonal
 //             slot rho = g only for the k-blocks not above its column block) it produces the kernel values of k-block
-//             4 (g + 1) + w for the next group in micro-steps between its MFMAs, adds their share of the mean, and
-//             stores them; one workgroup barrier per group.
+//             4 (g + 1) + w for the next group, adds their share of the mean, and stores them; one workgroup barrier per
+//             group.  The source places the production's micro-steps between the MFMAs of k-blocks 1..3; the code object
+//             does not: the compiler sinks the side-effect-free chain through the basic blocks of the `cw >= i` branches
+//             (sched_barrier orders within a block only), so in every group the production's VALU instructions and its
+//             distance MFMAs form one block behind the group's last variance MFMA, in front of the LDS store and the
+//             barrier.  Every timing of this kernel was taken on that form; pinned in place the steps cost 12 registers
+//             and the kernel is slower (KERNELS.md 4.1).
 //   operands  each wave streams its own slice of L^-T, packed in consumption order (bbh_pack_coop_kernel), through the
 //             8-deep register ring of the windowed form.  The slice has the same shape for every wave (the inactive
 //             part of the diagonal slot is stored as zeros and skipped by a wave-uniform branch), so ring slots and
@@ -38,6 +43,10 @@
 #ifndef BBH_COOP_PAIRS
 #define BBH_COOP_PAIRS 4  // operand ring: register pairs (two fragments each) in flight per wave
 #endif
+// Candidate fragments once per workgroup (wave w builds the k-steps k = w (mod 4), the others read them from LDS) - every
+// instantiation but the two-round seeded one with three k-steps and the table, which spills one register at its 96-register cap
+// with it and keeps the set-up in which every wave builds all fragments (GMIN: bbh_coop_posterior_kernel).
+__host__ __device__ constexpr bool coop_share_cf(int KD, int KVF, int GMIN) { return !(GMIN >= 6 && KD == 3 && (KVF & 9) == 9); }
 #ifndef BBH_COOP_ABLATE_BARRIER
 #define BBH_COOP_ABLATE_BARRIER 0
 #endif
@@ -89,6 +98,7 @@ struct CoopArgs {
   int g0;                 // first group that exists: 8 - nb / 4
   // seeded distance GEMM (KVF bit 8): f.trainfrag is the stream without the two augmentation rows, scaled by sqrt(5), and
   const double* na = nullptr;  // [16 nb] the training rows' squared norms in the same coordinates (padding rows: far-away marker)
+  const double* alna = nullptr;  // [alpha 16 nb | na 16 nb], 16-byte aligned: the image the kernel copies to LDS; na points into it
 };
 
 // fragments of the groups before G (in the full 8-round numbering)
@@ -117,8 +127,11 @@ __device__ __forceinline__ void coop_group(const WaveCtx (&c)[NT], const double*
   constexpr int REM = OPEN ? (1 << 20) : coop_frags_before(BBH_COOP_ROUNDS) - coop_frags_before(G + 1);  // fragments after this group
   constexpr int HOSTS = 12 * FULL;  // MFMA slots of k-blocks 1..3 that carry the micro-steps of the production
   constexpr int STEPS = NT * BBH_KV_STEPS;  // micro-steps of this wave's production: tile 0's, then tile 1's
+  constexpr bool TFPAIR = SEED;                    // the seeded stream stores its training fragments in pairs of k-steps
+  constexpr int NTF = TFPAIR ? (KD + 1) / 2 : KD;  // vector-memory loads per production
   const unsigned lane8 = (unsigned)c[0].l * 8u, lane16 = (unsigned)c[0].l * 16u;
   double tfv[KD];
+  d2 tfp[(KD + 1) / 2];
   d4 dsa[NT], dsb[NT];
   KvState<BBH_KV_NU> P;
   double kv[NT][4], kvx[NT][4], kvn[NT][4], alv[4], nav[4];
@@ -126,7 +139,13 @@ __device__ __forceinline__ void coop_group(const WaveCtx (&c)[NT], const double*
 #pragma unroll
     for (int r = 0; r < 4; r++) nav[r] = na_next[4 * r];
   }
-  if constexpr (PRODUCE) {
+  if constexpr (PRODUCE && TFPAIR) {  // pair p = k-steps 2 p, 2 p + 1 at byte 1024 p + 16 lane; an odd last k-step alone behind them
+    static_for<0, KD / 2>([&](auto pc) __attribute__((always_inline)) {
+      constexpr int p = decltype(pc)::value;
+      coop_gload2<(p % 4) * 1024>(tfp[p], tfn + (p / 4) * 512, lane16);
+    });
+    if constexpr (KD % 2 == 1) coop_gload<((KD - 1) % 8) * 512>(tfv[KD - 1], tfn + ((KD - 1) / 8) * 512, lane8);
+  } else if constexpr (PRODUCE) {
     static_for<0, KD>([&](auto kc) __attribute__((always_inline)) {
       constexpr int k = decltype(kc)::value;
       coop_gload<(k % 8) * 512>(tfv[k], tfn + (k / 8) * 512, lane8);
@@ -156,9 +175,9 @@ __device__ __forceinline__ void coop_group(const WaveCtx (&c)[NT], const double*
         constexpr int pr = f / 2;
         if constexpr (f % 2 == 0 && !BBH_COOP_ABLATE_LOADS) {
           // pair loads younger than pair pr: NP - 1 (fewer at the very end of the slice), plus - for the pairs that
-          // were already in flight when this group's training fragments were requested - those KD loads
+          // were already in flight when this group's training fragments were requested - those NTF loads
           constexpr int BEHIND = ((TOT + REM) / 2 - 1 - pr) < (NP - 1) ? ((TOT + REM) / 2 - 1 - pr) : (NP - 1);
-          coop_vmwait2<BEHIND + ((PRODUCE && pr < NP) ? KD : 0)>(ring[pr % NP]);
+          coop_vmwait2<BEHIND + ((PRODUCE && pr < NP) ? NTF : 0)>(ring[pr % NP]);
         }
 #if BBH_COOP_ABLATE_CHAIN  // timing experiment (wrong results): every MFMA goes to the accumulator (f mod 8)
         static_for<0, NT>([&](auto tc_) __attribute__((always_inline)) {
@@ -193,8 +212,16 @@ __device__ __forceinline__ void coop_group(const WaveCtx (&c)[NT], const double*
         __builtin_amdgcn_sched_barrier(0);
       });
       if constexpr (PRODUCE && i == 0 && r == 3) {
-        coop_vmwait<NP>(tfv[KD - 1]);  // the NP pair loads in flight are all younger than the training fragments
+        // the NP pair loads in flight are all younger than the training fragments; the wait is tied to the youngest of those
+        if constexpr (TFPAIR && KD % 2 == 0)
+          coop_vmwait2<NP>(tfp[KD / 2 - 1]);
+        else
+          coop_vmwait<NP>(tfv[KD - 1]);
         __builtin_amdgcn_sched_barrier(0);
+        if constexpr (TFPAIR) {
+#pragma unroll
+          for (int k = 0; k + 1 < KD; k += 2) tfv[k] = tfp[k / 2][0], tfv[k + 1] = tfp[k / 2][1];
+        }
         if constexpr (!BBH_COOP_ABLATE_KV) {
           static_for<0, NT>([&](auto tc_) __attribute__((always_inline)) {
             constexpr int t = decltype(tc_)::value;
@@ -248,10 +275,13 @@ __global__ __launch_bounds__(256, (GMIN >= 6 ? 5 : GMIN >= 4 ? 4 : BBH_COOP_WAVE
 
   WaveCtx c[NT];
   int tcs[NT];
-  // candidate fragments: b = x * scl + ofs, augmented with [1, |b|^2]; every wave builds the tiles' fragments itself.
-  // Loads first, all of them unconditional (clamped index) and independent: written as `if (dim < dn) v = fma(xr[numcol[dim]],
-  // ...)` every k-step became its own divergent block - column index, wait, row value, wait - twelve dependent memory round
-  // trips per tile before the first kernel value could be computed.
+  // candidate fragments: b = x * scl + ofs, augmented with [1, |b|^2] (seeded form: sqrt(5) b, no augmentation).  The four waves
+  // share the work, one k-step in four each, and exchange the fragments through LDS (coop_share_cf); the norm |b|^2 every
+  // wave forms itself from the exchanged fragments.  Otherwise every wave builds all fragments itself: loads first, all of
+  // them unconditional (clamped index) and independent - written as `if (dim < dn) v = fma(xr[numcol[dim]], ...)` every k-step
+  // became its own divergent block - column index, wait, row value, wait - twelve dependent memory round trips per tile before
+  // the first kernel value could be computed.
+  constexpr bool CFSHARE = coop_share_cf(KD, KVF, GMIN);
   int xcol[KD];
   double xval[NT][KD], xscl[KD], xofs[KD];
   const double* xr[NT];
@@ -259,7 +289,18 @@ __global__ __launch_bounds__(256, (GMIN >= 6 ? 5 : GMIN >= 4 ? 4 : BBH_COOP_WAVE
   // the candidate-row loads instead of following them (the per-tile set-up is a chain of memory round trips: at n = 128 a tile
   // is 8 us of which the MFMA work is 5)
   double tfv0[KD];
-  kvp_load<KD>(a.trainfrag + l, w, tfv0);
+  if constexpr (SEED) {  // pairs of k-steps, lane-interleaved (host_pack_trainfrag_seeded)
+    const double* t0 = a.trainfrag + (int64_t)w * KD * 64;
+#pragma unroll
+    for (int k = 0; k + 1 < KD; k += 2) {
+      const d2 pr = *(const d2*)(t0 + k * 64 + 2 * l);
+      tfv0[k] = pr[0];
+      tfv0[k + 1] = pr[1];
+    }
+    if constexpr (KD % 2 == 1) tfv0[KD - 1] = t0[(KD - 1) * 64 + l];
+  } else {
+    kvp_load<KD>(a.trainfrag + l, w, tfv0);
+  }
   double na0[4];  // SEED: the squared norms of k-block w's rows, from memory (the LDS copy is not complete before the first barrier)
   if constexpr (SEED) {
 #pragma unroll
@@ -270,26 +311,61 @@ __global__ __launch_bounds__(256, (GMIN >= 6 ? 5 : GMIN >= 4 ? 4 : BBH_COOP_WAVE
     const int64_t row = (tile0 + 16 * t + cnd < a.N) ? tile0 + 16 * t + cnd : a.N - 1;
     xr[t] = a.X + row * a.ldx;
   }
-  if (a.numcol_identity) {  // the numerical columns are the leading comp-rep columns, in order: no index round trip
+  // wave-uniform stream pointer + lane index: scalar base / 32-bit lane offset addressing (no 64-bit VALU pointer
+  // arithmetic).  The first fragments are requested before the first kernel values are computed (and before the barrier of the
+  // candidate-fragment exchange): their L2 latency passes under that work (the compiler's own wait for the training fragments
+  // below also covers these older loads).
+  const double* rs = ca.rstream + (int64_t)w * ca.frags * 64;
+  d2 ring[BBH_COOP_PAIRS];
+  auto ring_first = [&]() __attribute__((always_inline)) {
+    static_for<0, BBH_COOP_PAIRS>([&](auto ic) __attribute__((always_inline)) {
+      constexpr int i = decltype(ic)::value;
+      coop_gload2<(i % 4) * 1024>(ring[i], rs + (i / 4) * 512, (unsigned)l * 16u);
+    });
+  };
+  if constexpr (CFSHARE) {
+    // once per workgroup: wave w loads and scales the k-steps k = w (mod 4) and leaves them in the kernel-value buffer, which
+    // nothing writes before the barrier behind the first production; at most (KD + 3) / 4 wave-uniform trips
+    for (int k = w; k < KD; k += 4) {
+      const int dim = 4 * k + q, dimc = dim < a.dn ? dim : a.dn - 1;
+      const int col = a.numcol_identity ? dimc : a.numcol[dimc];
+      const double sc = a.scl[dimc], of = a.ofs[dimc];
 #pragma unroll
-    for (int k = 0; k < KD; k++) xcol[k] = (4 * k + q < a.dn) ? 4 * k + q : a.dn - 1;
+      for (int t = 0; t < NT; t++) {
+        double v = (BBH_COOP_ABLATE_PRO & 2) ? 0.01 * (double)(dim + cnd) : fma(xr[t][col], sc, of);
+        if constexpr (SEED) v *= BBH_SQRT5;  // as the training side (host_pack_trainfrag_seeded): sqrt(5) times the scaled coordinate
+        s_kv[t * BBH_COOP_KV_TILE + k * 64 + l] = dim < a.dn ? v : 0.0;
+      }
+    }
   } else {
+    if (a.numcol_identity) {  // the numerical columns are the leading comp-rep columns, in order: no index round trip
 #pragma unroll
-    for (int k = 0; k < KD; k++) xcol[k] = a.numcol[(4 * k + q < a.dn) ? 4 * k + q : a.dn - 1];
+      for (int k = 0; k < KD; k++) xcol[k] = (4 * k + q < a.dn) ? 4 * k + q : a.dn - 1;
+    } else {
+#pragma unroll
+      for (int k = 0; k < KD; k++) xcol[k] = a.numcol[(4 * k + q < a.dn) ? 4 * k + q : a.dn - 1];
+    }
+#pragma unroll
+    for (int k = 0; k < KD; k++) {
+      const int dimc = (4 * k + q < a.dn) ? 4 * k + q : a.dn - 1;
+#pragma unroll
+      for (int t = 0; t < NT; t++) xval[t][k] = xr[t][xcol[k]];
+      xscl[k] = a.scl[dimc];
+      xofs[k] = a.ofs[dimc];
+    }
   }
-#pragma unroll
-  for (int k = 0; k < KD; k++) {
-    const int dimc = (4 * k + q < a.dn) ? 4 * k + q : a.dn - 1;
-#pragma unroll
-    for (int t = 0; t < NT; t++) xval[t][k] = xr[t][xcol[k]];
-    xscl[k] = a.scl[dimc];
-    xofs[k] = a.ofs[dimc];
+  // alpha (and |a|^2) -> LDS: requested after the candidate-row loads, so that its round trip passes under theirs
+  if constexpr (SEED) {  // one contiguous image of both (host_pack_trainfrag_seeded), 16 bytes per lane and trip
+    if (!(BBH_COOP_ABLATE_PRO & 1))
+      for (int s = threadIdx.x; s < 16 * a.nb; s += 256) ((d2*)s_mem)[s] = ((const d2*)ca.alna)[s];
+  } else {
+    if (!(BBH_COOP_ABLATE_PRO & 1))
+      for (int s = threadIdx.x; s < 16 * a.nb; s += 256) s_alpha[s] = a.meanB[(int64_t)s * 16];
   }
-  // alpha -> LDS: requested after the candidate-row loads, so that its round trip passes under theirs
-  if (!(BBH_COOP_ABLATE_PRO & 1))
-    for (int s = threadIdx.x; s < 16 * a.nb; s += 256) s_alpha[s] = a.meanB[(int64_t)s * 16];
-  if constexpr (SEED)
-    for (int s = threadIdx.x; s < 16 * a.nb; s += 256) s_na[s] = ca.na[s];
+  if constexpr (CFSHARE) {
+    ring_first();
+    __syncthreads();  // the tile's candidate fragments are in LDS
+  }
 #pragma unroll
   for (int t = 0; t < NT; t++) {
     double nbsum = 0.0;
@@ -297,7 +373,10 @@ __global__ __launch_bounds__(256, (GMIN >= 6 ? 5 : GMIN >= 4 ? 4 : BBH_COOP_WAVE
     for (int k = 0; k < KD; k++) {
       const int dim = 4 * k + q;
       double v = 0.0;
-      if (dim < a.dn) {
+      if constexpr (CFSHARE) {
+        v = s_kv[t * BBH_COOP_KV_TILE + k * 64 + l];  // zero beyond the model's dimensions
+        nbsum = fma(v, v, nbsum);
+      } else if (dim < a.dn) {
         v = (BBH_COOP_ABLATE_PRO & 2) ? 0.01 * (double)(dim + cnd) : fma(xval[t][k], xscl[k], xofs[k]);
         if constexpr (SEED) v *= BBH_SQRT5;  // as the training side (host_pack_trainfrag_seeded): sqrt(5) times the scaled coordinate
         nbsum = fma(v, v, nbsum);
@@ -353,15 +432,7 @@ __global__ __launch_bounds__(256, (GMIN >= 6 ? 5 : GMIN >= 4 ? 4 : BBH_COOP_WAVE
 #pragma unroll
     for (int s = 0; s < BBH_COOP_ROUNDS; s++) acc[t][s] = (d4){0.0, 0.0, 0.0, 0.0};
   }
-  // wave-uniform stream pointer + lane index: scalar base / 32-bit lane offset addressing (no 64-bit VALU pointer
-  // arithmetic).  The first fragments are requested before the first kernel values are computed: their L2 latency
-  // passes under that work (the compiler's own wait for the training fragments below also covers these older loads).
-  const double* rs = ca.rstream + (int64_t)w * ca.frags * 64;
-  d2 ring[BBH_COOP_PAIRS];
-  static_for<0, BBH_COOP_PAIRS>([&](auto ic) __attribute__((always_inline)) {
-    constexpr int i = decltype(ic)::value;
-    coop_gload2<(i % 4) * 1024>(ring[i], rs + (i / 4) * 512, (unsigned)l * 16u);
-  });
+  if constexpr (!CFSHARE) ring_first();
   {  // the first group's kernel values: wave w produces k-block w, not overlapped with anything
     double tfv[KD], kv0[NT][4];
     if constexpr (BBH_COOP_ABLATE_PRO & 4) {

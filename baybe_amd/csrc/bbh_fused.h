@@ -314,7 +314,10 @@ __device__ __forceinline__ void kvp_dist_seeded(const WaveCtx& c, const double (
 // Kernel values of NU (= 4) scaled squared distances in lockstep, cut into BBH_KV_STEPS micro-steps of NU to
 // 2 NU VALU instructions so that the caller can place them between MFMAs in program order (the compiler's
 // scheduler clumps library sqrt()/exp() calls behind the MFMAs even when asked to interleave them
-// with sched_group_barrier).  Matérn-5/2: k(r2) = (1 + s + s^2/3) exp(-s), s = sqrt(5 r2); Matérn-3/2:
+// with sched_group_barrier).  Program order is kept within a basic block only: where the caller's MFMAs sit in
+// blocks of their own (the wave-uniform `cw >= i` branches of coop_group) the compiler sinks the chain behind them all the
+// same (pinning every step's results with empty volatile assembly keeps them in place, and costs 12 registers and time:
+// KERNELS.md 4.1).  Matérn-5/2: k(r2) = (1 + s + s^2/3) exp(-s), s = sqrt(5 r2); Matérn-3/2:
 // (1 + s) exp(-s), s = sqrt(3 r2); RBF: exp(-r2 / 2) (the sqrt steps are skipped):
 //   sqrt: v_rsq_f64 seed and one Newton step (error 1.5 eps^2 = 3e-16; the Goldschmidt + Newton form
 //         with error O(eps^4) is kept behind BBH_KV_SQRT_NR=0 and measured 1 % slower);

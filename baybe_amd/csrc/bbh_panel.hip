@@ -195,11 +195,16 @@ static void host_pack_trainfrag(const bbh_handle* h, const double* pts, int64_t 
 // followed by na[16 nb] = |A_i|^2 (what the kernel seeds the accumulator with).  The Matérn-5/2 constant is folded into the
 // coordinates - the candidate side multiplies its scaled coordinate by the same sqrt(5) - so the GEMM delivers t = 5 r2.
 // Padding rows: zero fragments and the far-away marker of the augmented stream in these coordinates (5e8: the value underflows to 0).
+// Consecutive k-steps are stored lane-interleaved like the operand pairs (pair p of block tb, lane l: [k-step 2 p | 2 p + 1] at
+// double (tb kds + 2 p) 64 + 2 l; an odd last k-step stays a plain fragment): one 16-byte load per lane fetches two.  Between the
+// fragments and na there is room for alpha[16 nb] (filled on the device by bbh_pack_operands): the two together are the image the
+// kernel copies to LDS.
 static void host_pack_trainfrag_seeded(const bbh_handle* h, const double* pts, int64_t cnt, int64_t nb, int kds, std::vector<double>& out) {
   const int dn = h->dn;
   const double* ls = h->theta.data() + 3;
-  out.assign((size_t)nb * kds * 64 + (size_t)16 * nb, 0.0);
-  double* na = out.data() + (size_t)nb * kds * 64;
+  const size_t alpha_room = (size_t)16 * nb;
+  out.assign((size_t)nb * kds * 64 + alpha_room + (size_t)16 * nb, 0.0);
+  double* na = out.data() + (size_t)nb * kds * 64 + alpha_room;
   std::vector<double> a(dn);
   for (int64_t tb = 0; tb < nb; tb++)
     for (int c16 = 0; c16 < 16; c16++) {
@@ -214,7 +219,12 @@ static void host_pack_trainfrag_seeded(const bbh_handle* h, const double* pts, i
         sum += a[j] * a[j];
       }
       na[i] = sum;
-      for (int dim = 0; dim < dn; dim++) out[((size_t)tb * kds + dim / 4) * 64 + (dim % 4) * 16 + c16] = -2.0 * a[dim];
+      for (int dim = 0; dim < dn; dim++) {
+        const int k = dim / 4, l = (dim % 4) * 16 + c16;
+        const bool paired = (k | 1) < kds;  // k-steps k & ~1 and k | 1 share a pair
+        const size_t at = paired ? ((size_t)tb * kds + (k & ~1)) * 64 + 2 * l + (k & 1) : ((size_t)tb * kds + k) * 64 + l;
+        out[at] = -2.0 * a[dim];
+      }
     }
 }
 
@@ -439,6 +449,8 @@ int bbh_pack_operands(bbh_handle* h) {
           h->tf_s_elems = (int64_t)tfs.size();
         }
         BBH_HIP_TRY(h, hipMemcpyAsync(h->d_trainfrag_s, tfs.data(), sizeof(double) * tfs.size(), hipMemcpyHostToDevice, s));
+        // alpha in front of the squared norms (np = 16 nb values; the padding rows' are zero)
+        BBH_HIP_TRY(h, hipMemcpyAsync(h->d_trainfrag_s + (size_t)nb * h->coop_kds * 64, h->d_alpha, sizeof(double) * np, hipMemcpyDeviceToDevice, s));
         BBH_HIP_TRY(h, hipStreamSynchronize(s));  // (pageable staging vector)
       }
     }
@@ -743,7 +755,8 @@ int bbh_launch_fused(bbh_handle* h, const double* X_dev, int64_t N, int64_t ldx,
     h->last_seeded = h->coop_kds > 0;
     if (h->coop_kds) {  // seeded distance GEMM: its own training fragments, the squared norms next to alpha in LDS (+ 4 KB at n = 512)
       ca.f.trainfrag = h->d_trainfrag_s;
-      ca.na = h->d_trainfrag_s + (size_t)h->nb * h->coop_kds * 64;
+      ca.alna = h->d_trainfrag_s + (size_t)h->nb * h->coop_kds * 64;
+      ca.na = ca.alna + 16 * (size_t)h->nb;
       const size_t clds = sizeof(double) * (32 * (size_t)h->nb + (2 * 4 * 256 + 128));
       if (!bbh_coop_seed_launch(h->coop_kds, has_tbl, cgrid, clds, h->stream, ca, h->sw.coop_small)) {
         h->err = "cooperative posterior form: no seeded instantiation for this model although its operands were packed";
