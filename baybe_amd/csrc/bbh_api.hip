@@ -143,6 +143,7 @@ extern "C" int bbh_destroy(bbh_handle* h) {
   bbh_sobol_destroy(h);
   bbh_fps_destroy(h);
   bbh_flow_destroy(h);
+  bbh_postgrad_destroy(h);
   bbh_free_model_public(h);
   if (h->d_ws) hipFree(h->d_ws);
   if (h->fit_stream) {

@@ -402,6 +402,7 @@ struct bbh_handle {
   void* select_state = nullptr;   // chunk keys, result block and base-sample tables of the selection kernels (bbh_select.hip)
   void* sobol_state = nullptr;    // staging of the device-side base-sample draw (bbh_sobol.hip), null until bbh_sobol_normal_dev
   void* fps_state = nullptr;      // keys, minimum distances and result blocks of farthest point sampling (bbh_fps.hip)
+  void* postgrad_state = nullptr; // (K + s2 I)^-1 and column constants of the current factorisation (bbh_postgrad.hip), null until bbh_posterior_grad
   // timing
   int timing = 0;  // 0 off, 1 every kernel family, otherwise 2 x (bit mask of the families that record events)
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -506,6 +507,8 @@ void bbh_sobol_destroy(bbh_handle* h);   // bbh_sobol.hip
 void bbh_fps_destroy(bbh_handle* h);     // bbh_fps.hip
 void bbh_fps_reset(bbh_handle* h);       // bbh_fps.hip: ends the selection in progress (it points into caller-owned memory)
 void bbh_flow_destroy(bbh_handle* h);    // bbh_fitflow.hip
+void bbh_postgrad_destroy(bbh_handle* h);     // bbh_postgrad.hip
+void bbh_postgrad_invalidate(bbh_handle* h);  // bbh_postgrad.hip: a new factorisation - the cached (K + s2 I)^-1 is stale
 bool bbh_fit_flow_launch(bbh_handle* h, const double* theta_dev, double* out_dev, int* info_dev, bool tail_only, const double* theta_host = nullptr,
                          bool split = false, int skip_mt = 0, bool prepare_only = false);  // split: two launches - the factorisation with K^-1's tiles, then everything behind them; skip_mt: tail form without the M-tile roles
 bool bbh_fit_flow_mt_args(bbh_handle* h, void* pd_mt_args_out);  // arguments for K^-1's tiles inside the factorisation launch, matching the next tail launch  // 64 < np <= 1024: the whole evaluation as one dataflow launch, or (tail_only) everything after the factorisation; false: not eligible

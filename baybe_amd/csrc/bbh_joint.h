@@ -23,7 +23,8 @@
 __device__ __forceinline__ int tri(int i, int j) { return i * (i + 1) / 2 + j; }
 
 template <typename ST>  // ST: type of the stride (int 64, int64_t N)
-__device__ __forceinline__ bool bbh_joint_factor(double* L, ST stride, int p, double v0, const double* cross_i, const double* cov_pp) {
+__device__ __forceinline__ bool bbh_joint_factor(double* L, ST stride, int p, double v0, const double* cross_i, const double* cov_pp,
+                                                 double* jitter_used = nullptr) {  // jitter_used: the diagonal jitter of the last attempt
   const int q = p + 1;
   double jitter = 0.0;
   bool ok = false;
@@ -51,6 +52,7 @@ __device__ __forceinline__ bool bbh_joint_factor(double* L, ST stride, int p, do
         }
       }
     }
+    if (jitter_used) *jitter_used = jitter;
     if (!ok) jitter = 1e-8 * pow(10.0, (double)attempt);
   }
   return ok;

@@ -1007,6 +1007,7 @@ extern "C" int bbh_factorize(bbh_handle* h, const double* theta_host, double* ji
   int rc = bbh_upload_theta(h, theta_host);
   if (rc) return rc;
   h->factorized = false;
+  bbh_postgrad_invalidate(h);
   if (bbh_is_rff(h)) {
     rc = bbh_rff_factorize(h);
     if (rc) return rc;

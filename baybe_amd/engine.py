@@ -945,6 +945,59 @@ class HipGP:
         )
         return scores
 
+    # ---- derivatives for gradient-based continuous optimisation ---------------------------
+    def posterior_grad(self, X, cols):
+        """Posterior of N candidates and its derivatives with respect to the raw coordinates of the comp-rep columns ``cols``
+        (ascending, numerical; ``bbh_posterior_grad``): a dict of device tensors ``mean`` [N], ``var`` [N], ``cross`` [N, p],
+        ``dmean`` [N, dc], ``dvar`` [N, dc], ``dcross`` [N, p, dc], p = the pending points set on the handle."""
+        torch = self._torch()
+        X = self._as_dev(X)
+        N = X.shape[0]
+        cols = np.ascontiguousarray(cols, dtype=np.int32).reshape(-1)
+        dc, p = int(cols.shape[0]), getattr(self, "_p", 0)
+        new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=X.device)  # noqa: E731
+        out = {"mean": new(N), "var": new(N), "cross": new(N, p), "dmean": new(N, dc), "dvar": new(N, dc), "dcross": new(N, p, dc)}
+        self._check(
+            self._lib.bbh_posterior_grad(
+                self._h, X.data_ptr(), N, X.stride(0), cols.ctypes.data_as(C.POINTER(C.c_int32)), dc, out["mean"].data_ptr(),
+                out["var"].data_ptr(), out["cross"].data_ptr() if p else None, out["dmean"].data_ptr(), out["dvar"].data_ptr(),
+                out["dcross"].data_ptr() if p else None,
+            ),
+            "bbh_posterior_grad",
+        )
+        return out
+
+    def qlogei_partials(self, mean, var, cross, z: np.ndarray, best_f: float, sign: float = 1.0):
+        """qLogEI of the t-batches [x_i ; pending] and its partial derivatives with respect to (mean_i, var_i, cross_i1 .. cross_ip)
+        (``bbh_qlogei_partials``): (scores [N], partials [N, 2 + p], ok [N] uint8) as device tensors; ``ok`` = 0 marks a candidate
+        whose variance is not positive or whose joint factor needed jitter (zero partials)."""
+        torch = self._torch()
+        p = getattr(self, "_p", 0)
+        z = np.ascontiguousarray(z, dtype=np.float64).reshape(-1, 1 + p)
+        N = mean.shape[0]
+        scores = torch.empty(N, dtype=torch.float64, device=mean.device)
+        part = torch.empty((N, 2 + p), dtype=torch.float64, device=mean.device)
+        ok = torch.empty(N, dtype=torch.uint8, device=mean.device)
+        self._check(
+            self._lib.bbh_qlogei_partials(
+                self._h, mean.data_ptr(), var.data_ptr(), cross.data_ptr() if p else None, N, _dp(z), z.shape[0], float(best_f),
+                float(sign), scores.data_ptr(), part.data_ptr(), ok.data_ptr(),
+            ),
+            "bbh_qlogei_partials",
+        )
+        return scores, part, ok
+
+    def qlogei_value_grad(self, X, cols, z: np.ndarray, best_f: float, sign: float = 1.0):
+        """qLogEI of [x_i ; pending] and its gradient with respect to the columns ``cols`` of x_i: the two native calls, then the
+        chain rule grad_j = a_m dmean_j + a_v dvar_j + sum_r a_r dcross_rj as one contraction on the device.  Returns
+        (scores [N], grad [N, dc], ok [N] uint8) as device tensors."""
+        g = self.posterior_grad(X, cols)
+        scores, part, ok = self.qlogei_partials(g["mean"], g["var"], g["cross"], z, best_f, sign)
+        grad = part[:, 0:1] * g["dmean"] + part[:, 1:2] * g["dvar"]
+        if g["cross"].shape[1]:
+            grad = grad + (part[:, 2:, None] * g["dcross"]).sum(dim=1)
+        return scores, grad, ok
+
     def sobol_normal_dev(self, S: int, q: int, seed: int):
         """[S, q] base samples of ``SobolQMCNormalSampler`` as a device tensor, produced on the device (``bbh_sobol_normal_dev``;
         asynchronous on the handle's stream): what ``sobol_normal_base_samples`` returns, up to the last bits of erfinv."""

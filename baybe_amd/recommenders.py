@@ -36,6 +36,10 @@ from baybe_amd.surrogates import HipCompositeImpl, HipGaussianProcessSurrogate, 
 
 
 MAX_HYBRID_CONTINUOUS = 4  # continuous parameters of a hybrid / continuous space the derivative-free search is validated for
+MAX_GRADIENT_CONTINUOUS = 32  # ... and the gradient-based refinement takes (the differentiated columns of one bbh_posterior_grad call)
+MAX_GRADIENT_TRAINING_POINTS = 512  # training points of a model bbh_posterior_grad differentiates
+MAX_GRADIENT_STARTS = 16384  # starts one gradient refinement advances together
+GRADIENT_KERNELS = ("matern32", "matern52", "rbf")
 
 
 def _hash_buffers(bufs) -> int:
@@ -134,9 +138,9 @@ def _check_objective(objective, acqf):
     return program
 
 
-def _check_continuous_part(cont) -> None:
+def _check_continuous_part(cont, optimizer: str = "compass") -> None:
     """What of ``SubspaceContinuous`` the HIP path's search handles: box-bounded parameters.  Linear / nonlinear / cardinality /
-    interpoint constraints need the reference's constrained optimiser."""
+    interpoint constraints need the reference's constrained optimiser.  ``optimizer``: the recommender's ``continuous_optimizer``."""
     for name in ("constraints_lin_eq", "constraints_lin_ineq", "constraints_nonlin", "constraints_cardinality"):
         if len(getattr(cont, name, ()) or ()):
             raise IncompatibilityError(
@@ -144,11 +148,53 @@ def _check_continuous_part(cont) -> None:
                 f"Use BotorchRecommender."
             )
     dc = len(getattr(getattr(cont, "comp_rep_bounds", None), "columns", ()))
+    if optimizer == "gradient":
+        if dc > MAX_GRADIENT_CONTINUOUS:  # (before anything is fitted)
+            raise IncompatibilityError(
+                f"{dc} continuous parameters: continuous_optimizer='gradient' differentiates up to {MAX_GRADIENT_CONTINUOUS} of them "
+                f"on the device; use BotorchRecommender beyond that.")
+        return
     if dc > MAX_HYBRID_CONTINUOUS:  # (before anything is fitted)
         raise IncompatibilityError(
             f"{dc} continuous parameters: the HIP path searches the continuous box derivative-free (Sobol raw samples + pattern "
             f"search) and is held to the reference's enumeration (optimize_acqf_mixed) for up to {MAX_HYBRID_CONTINUOUS} of them "
             f"(tests/test_hybrid_gpu.py); use BotorchRecommender, whose gradient optimiser is the tool beyond that.")
+
+
+def _gradient_kernel_refusal(surrogate, searchspace):
+    """Why the surrogate's kernel has no device-side derivative (None: it has) - decided from the surrogate's settings and the
+    search space's encoding alone, before anything is fitted."""
+    use = "use continuous_optimizer='compass' (up to 4 continuous parameters) or BotorchRecommender"
+    if not hasattr(surrogate, "kernel_or_factory"):
+        return f"continuous_optimizer='gradient' needs the Gaussian process surrogate, not '{type(surrogate).__name__}'; {use}."
+    kernel = surrogate.kernel if surrogate.kernel_or_factory is None else surrogate.kernel_or_factory
+    bounds = np.asarray(searchspace.scaling_bounds.to_numpy(), dtype=np.float64)
+    d = bounds.shape[1]
+    if getattr(surrogate, "preset", "BAYBE") != "BAYBE":
+        from baybe_amd.gp_spec import from_preset
+
+        spec = from_preset(surrogate.preset, d, bounds[0], bounds[1])
+    elif isinstance(kernel, str):
+        spec = None
+        name = kernel
+    elif callable(kernel) and not hasattr(kernel, "to_gpytorch") and not hasattr(kernel, "lengthscale_prior"):
+        return (f"continuous_optimizer='gradient' must know the kernel before the fit; a kernel factory decides it from the training "
+                f"data. Pass a Matern-3/2, Matern-5/2 or RBF kernel, or {use}.")
+    else:
+        from baybe_amd.gp_spec import GPSpec
+        from baybe_amd.kernels import apply_kernel_spec
+
+        spec = GPSpec.baybe_default(d, bounds[0], bounds[1])
+        apply_kernel_spec(spec, kernel, searchspace)
+    if spec is not None:
+        if spec.n_factors > 1 or spec.has_subsets:
+            return (f"continuous_optimizer='gradient' differentiates a single Matern-3/2, Matern-5/2 or RBF kernel over all numerical "
+                    f"columns, not a composite kernel or one on a parameter subset; {use}.")
+        name = spec.kernel
+    if name not in GRADIENT_KERNELS:
+        return (f"continuous_optimizer='gradient' differentiates Matern-3/2, Matern-5/2 and RBF kernels; the kernel '{name}' (RFF, "
+                f"piecewise-polynomial, rational-quadratic, periodic, dot-product, Matern-1/2) has no derivative on the device; {use}.")
+    return None
 
 
 class HipRecommenderImpl:
@@ -221,13 +267,15 @@ class HipRecommenderImpl:
 
     def _setup_acqf(self, searchspace, objective, measurements, pending_experiments=None, acquisition_function=None):
         """Native counterpart of ``_setup_botorch_acqf``: fit (cached), best_f, pending rows."""
+        cont = getattr(searchspace, "continuous", None)
+        if self.continuous_optimizer == "gradient" and cont is not None and not getattr(cont, "is_empty", True):
+            self._check_gradient_context(searchspace, objective, measurements, acquisition_function)
         if getattr(self._surrogate_model, "is_ensemble", False):
             return self._setup_forest_acqf(searchspace, objective, measurements, pending_experiments, acquisition_function)
         if getattr(self._surrogate_model, "is_independent_gaussian", False):
             return self._setup_linear_acqf(searchspace, objective, measurements, pending_experiments, acquisition_function)
-        cont = getattr(searchspace, "continuous", None)
         if cont is not None and not getattr(cont, "is_empty", True):
-            _check_continuous_part(cont)  # hybrid / continuous spaces: box-bounded continuous parameters only
+            _check_continuous_part(cont, self.continuous_optimizer)  # hybrid / continuous spaces: box-bounded continuous parameters only
         self._objective = objective
         acqf = self._get_acquisition_function(objective, acquisition_function)
         self._program = _check_objective(objective, acqf)
@@ -287,6 +335,32 @@ class HipRecommenderImpl:
             eng = surrogate.engine
             self._best_f = eng.best_f(surrogate.sign) if self._program is None else eng.best_f(1.0, self._program)
         return surrogate, acqf
+
+    def _check_gradient_context(self, searchspace, objective, measurements, acquisition_function=None) -> None:
+        """What ``continuous_optimizer="gradient"`` covers - qLogEI of one untransformed target under a single-task GP with one
+        Matern-3/2 / Matern-5/2 / RBF kernel, at most 512 training points, one device - checked before anything is fitted; every
+        text says what to use instead."""
+        use = "use continuous_optimizer='compass' (up to 4 continuous parameters) or BotorchRecommender"
+        _check_continuous_part(searchspace.continuous, "gradient")
+        if _is_multi_output(objective):
+            raise IncompatibilityError(f"continuous_optimizer='gradient' handles single-target objectives, not multi-output ones; {use}.")
+        acqf = self._get_acquisition_function(objective, acquisition_function)
+        if getattr(acqf, "kind", None) != "qLogEI":
+            raise IncompatibleAcquisitionFunctionError(
+                f"continuous_optimizer='gradient' differentiates qLogExpectedImprovement only, not '{type(acqf).__name__}'; {use}.")
+        if _check_objective(objective, acqf) is not None:
+            raise IncompatibilityError(f"continuous_optimizer='gradient' has no derivative of a transformed target; {use}.")
+        if getattr(searchspace, "task_idx", None) is not None or int(getattr(searchspace, "n_tasks", 1)) > 1:
+            raise IncompatibilityError(f"continuous_optimizer='gradient' handles single-task models, not task parameters; {use}.")
+        why = _gradient_kernel_refusal(self._surrogate_model, searchspace)
+        if why is not None:
+            raise IncompatibilityError(why)
+        if measurements is not None and len(measurements) > MAX_GRADIENT_TRAINING_POINTS:
+            raise IncompatibilityError(
+                f"continuous_optimizer='gradient' differentiates models of up to {MAX_GRADIENT_TRAINING_POINTS} training points "
+                f"({len(measurements)} given); {use}.")
+        if self.shard is not None and getattr(self.shard, "world", 1) > 1:
+            raise IncompatibilityError(f"continuous_optimizer='gradient' runs on one device, not under row shards; {use}.")
 
     def _setup_forest_acqf(self, searchspace, objective, measurements, pending_experiments=None, acquisition_function=None):
         """``_setup_acqf`` for an ensemble surrogate (``baybe_amd.forest.HipRandomForestSurrogate``): what the forest path does not
@@ -595,7 +669,9 @@ class HipRecommenderImpl:
         from baybe_amd.engine import GreedyResult  # noqa: F401
 
         cont, disc = searchspace.continuous, searchspace.discrete
-        _check_continuous_part(cont)
+        gradient = self.continuous_optimizer == "gradient"
+        _check_continuous_part(cont, self.continuous_optimizer)
+        self._last_continuous_trace = []
         acqf, surrogate = self._acqf_in_use, self._surrogate_model
         if self._nehvi is not None:
             raise IncompatibilityError("Multi-output objectives (qLogNEHVI / qNEHVI / qLogNParEGO) and qNEI / qLogNEI in hybrid / continuous spaces are not on the HIP path; use BotorchRecommender.")
@@ -638,6 +714,12 @@ class HipRecommenderImpl:
         for _step in range(batch_size):
             pend = np.vstack([base] + picks) if picks else base
             scores = self._mc_or_analytic(eng, acqf, X, mean, var, pend, seed, self._sign(surrogate))
+            if gradient:
+                best_row = self._gradient_refine(eng, acqf, X, scores, Nd, R, dd, cb, pend, seed, self._sign(surrogate))
+                picks.append(best_row.reshape(1, -1))
+                if has_disc:
+                    pick_labels.append(labels[int(np.nonzero((D == best_row[:dd]).all(axis=1))[0][0])])
+                continue
             k = int(min(self.n_restarts, X.shape[0], 64))  # (bbh_topk returns at most 64 rows; the reference's n_restarts has no cap)
             _, top = eng.topk(scores, k)
             top = [int(t) for t in top if t >= 0]
@@ -680,6 +762,52 @@ class HipRecommenderImpl:
                 raise IncompatibleAcquisitionFunctionError("Analytic acquisition functions score single points only.")
             return self._analytic_scores(eng, acqf, mean, var, sign)
         return self._mc_scores_with_pending(eng, acqf, X, mean, var, pend, seed, sign)
+
+    def _gradient_refine(self, eng, acqf, X, scores, Nd: int, R: int, dd: int, cb: np.ndarray, pend, seed, sign):
+        """Gradient-based refinement of one greedy step.  Starts as the reference chooses them, per discrete row its ``n_restarts``
+        best raw samples (``optimize_acqf_mixed`` runs ``optimize_acqf`` per fixed-feature dictionary), restricted to the rows with
+        the best raw score so that at most ``MAX_GRADIENT_STARTS`` starts advance together; all of them climb qLogEI in their
+        continuous coordinates in ``maximize_box``, one device pass (``qlogei_value_grad``) per trial.  Returns the best final row
+        and leaves starts, final points and values on ``_last_continuous_trace``."""
+        import torch
+
+        from baybe_amd.continuous import maximize_box
+
+        if len(pend) > _lib.MAX_PENDING:
+            raise IncompatibilityError(
+                f"{len(pend)} pending / batch rows exceed the largest joint q-batch continuous_optimizer='gradient' differentiates "
+                f"({_lib.MAX_PENDING + 1} points); use continuous_optimizer='compass' or BotorchRecommender.")
+        k = int(min(self.n_restarts, R))
+        S2 = torch.nan_to_num(scores, nan=-float("inf")).view(Nd, R)
+        _, idx = torch.topk(S2, k, dim=1)  # [Nd, k] raw samples of every discrete row
+        rows = torch.arange(Nd, device=S2.device)
+        max_rows = max(1, MAX_GRADIENT_STARTS // k)
+        if Nd > max_rows:
+            rows = torch.sort(torch.topk(S2.max(dim=1).values, max_rows).indices).values
+        flat = (rows[:, None] * R + idx[rows]).reshape(-1)
+        starts_dev = X[flat].contiguous()
+        starts = starts_dev.cpu().numpy()
+        dc = starts.shape[1] - dd
+        cols = np.arange(dd, dd + dc, dtype=np.int32)
+        z = sobol_normal_base_samples(acqf.n_mc_samples, 1 + len(pend), seed)
+        eng.set_pending(pend if len(pend) else None)
+        disc_dev = starts_dev[:, :dd]
+
+        def value_and_grad(C):
+            Xc = torch.cat([disc_dev, torch.from_numpy(np.ascontiguousarray(C)).to(disc_dev.device)], dim=1).contiguous()
+            val, grad, ok = eng.qlogei_value_grad(Xc, cols, z, self._best_f, sign)
+            return val.cpu().numpy(), grad.cpu().numpy(), ok.cpu().numpy()
+
+        try:
+            res = maximize_box(value_and_grad, starts[:, dd:], cb[0], cb[1])
+        finally:
+            eng.set_pending(None)
+        final = np.hstack([starts[:, :dd], res.x])
+        vals = np.where(np.isfinite(res.values), res.values, -np.inf)
+        i = int(np.argmax(vals))
+        self._last_continuous_trace.append({"starts": starts, "final": final, "values": res.values.copy(), "best": i,
+                                            "iterations": res.iterations, "calls": res.calls})
+        return final[i]
 
     def _compass_refine(self, eng, acqf, starts: np.ndarray, dd: int, cb: np.ndarray, pend, seed, sign, iters: int = 24):
         """Compass (pattern) search on the continuous coordinates of ``starts`` [k, d], all starts advancing together: per
@@ -819,6 +947,15 @@ def _convert_hybrid_sampler(value):
     return value
 
 
+def _convert_continuous_optimizer(value):
+    """How the continuous coordinates of a hybrid / continuous recommendation are refined: "compass" (derivative-free pattern
+    search, up to 4 continuous parameters) or "gradient" (device-side derivatives, up to 32)."""
+    name = str(getattr(value, "value", value))
+    if name not in ("compass", "gradient"):
+        raise ValueError(f"'{value}' is not a valid continuous_optimizer (compass, gradient)")
+    return name
+
+
 def _validate_percentage(_, attribute, value):
     if not 0 <= value <= 1:  # botorch/core.py:123-135
         raise ValueError(f"Hybrid sampling percentage needs to be between 0 and 1 but is {value}")
@@ -839,6 +976,8 @@ def recommender_fields(with_base_fields: bool = True, surrogate_factory=HipGauss
         "sampling_percentage": field(default=1.0, validator=_validate_percentage, kw_only=True),
         "n_restarts": field(default=10, validator=[instance_of(int), gt(0)], kw_only=True),
         "n_raw_samples": field(default=64, validator=[instance_of(int), gt(0)], kw_only=True),
+        # refinement of the continuous coordinates: the pattern search, or - opt-in - gradient ascent on device-side derivatives
+        "continuous_optimizer": field(default="compass", converter=_convert_continuous_optimizer, kw_only=True),
         # optional baybe_amd.distributed.RowShard: this process scores only its row range and joins one all-gather
         # per selection step (multi-GPU)
         "shard": field(default=None, eq=False, repr=False, kw_only=True),
@@ -848,6 +987,8 @@ def recommender_fields(with_base_fields: bool = True, surrogate_factory=HipGauss
         "_nehvi": field(default=None, init=False, eq=False, repr=False),
         "_acqf_in_use": field(default=None, init=False, eq=False, repr=False),
         "_program": field(default=None, init=False, eq=False, repr=False),  # ObjectiveProgram of a transformed single target
+        # per greedy step of the last hybrid / continuous recommendation under "gradient": starts, final points, values (tests, timing)
+        "_last_continuous_trace": field(default=None, init=False, eq=False, repr=False),
     }
     if with_base_fields:
         f["acquisition_function"] = field(default=None, converter=convert_acqf, kw_only=True)

@@ -244,6 +244,27 @@ int bbh_qlogei_pending(bbh_handle* h, const double* mean_dev, const double* var_
                        const double* cross_dev, int64_t N, const double* z_host, int64_t S,
                        double best_f, double sign, const uint8_t* alive_dev, double* scores_dev);
 
+/* ---- derivatives for gradient-based continuous optimisation ----------------------------------------------------------------
+ * What the reference obtains by autograd through GPyTorch inside optimize_acqf / optimize_acqf_mixed
+ * (baybe/recommenders/pure/bayesian/botorch/hybrid.py:95-136, continuous.py): the posterior of N candidates AND its derivatives with
+ * respect to the raw comp-rep coordinates of the dc columns cols_host (ascending, each a numerical column of the model,
+ * 1 <= dc <= 32) - the chain rule through the input normalisation and the target standardisation is inside the call.  Conventions
+ * of bbh_posterior / bbh_cross_cov (original target scale, no observation noise); p = the handle's pending count:
+ *   mean_dev, var_dev [N], cross_dev [N, p];  dmean_dev, dvar_dev [N, dc], dcross_dev [N, p, dc]  (cross outputs may be NULL if p = 0).
+ * Models: one task, one Matern-3/2 / Matern-5/2 / RBF kernel (with or without outputscale), n <= 512; anything else returns -1 and
+ * bbh_last_error names the unmet condition.  Equal rows give equal bits, whatever their position and N.  Asynchronous. */
+int bbh_posterior_grad(bbh_handle* h, const double* X_dev, int64_t N, int64_t ldx, const int32_t* cols_host, int32_t dc,
+                       double* mean_dev, double* var_dev, double* cross_dev, double* dmean_dev, double* dvar_dev,
+                       double* dcross_dev);
+/* qLogEI of the t-batches [x_i ; pending] (p = 0: of x_i alone) from those statistics, scores_dev [N] as bbh_qlogei_q1 /
+ * bbh_qlogei_pending, and its partial derivatives part_dev [N, 2 + p] = (dA/dmean_i, dA/dvar_i, dA/dcross_i1 .. dA/dcross_ip).
+ * ok_dev [N]: 0 for a candidate whose variance is not > 0, whose joint factor needed jitter, or whose factor has a pivot below
+ * 1e-8 of its diagonal entry (a copy of a pending point) - its partials are 0, its score the value the value kernels return (the
+ * jittered one; NaN if no jitter level factors it).  z_host [S, 1 + p], S <= 8192.  Asynchronous. */
+int bbh_qlogei_partials(bbh_handle* h, const double* mean_dev, const double* var_dev, const double* cross_dev, int64_t N,
+                        const double* z_host, int64_t S, double best_f, double sign, double* scores_dev, double* part_dev,
+                        uint8_t* ok_dev);
+
 /* ---- the other acquisition functions of acqfs.py:161-290 on the same inputs ----------- */
 enum bbh_acq_kind {
   BBH_ACQ_QLOGEI = 0, BBH_ACQ_QEI = 1, BBH_ACQ_QPI = 2, BBH_ACQ_QSR = 3, BBH_ACQ_QUCB = 4, BBH_ACQ_QPSTD = 5,
