@@ -50,6 +50,12 @@ class ObjectiveProg(C.Structure):
     _fields_ = [("n_ops", C.c_int32), ("op", C.c_int32 * 8), ("p", (C.c_double * 3) * 8)]
 
 
+class Desirability(C.Structure):
+    """``bbh_desirability`` (include/baybe_hip.h): one objective program and weight per target, and the scalariser."""
+
+    _fields_ = [("n_targets", C.c_int32), ("scalarizer", C.c_int32), ("weight", C.c_double * 8), ("prog", ObjectiveProg * 8)]
+
+
 KERNEL_KINDS = {"matern12": 0, "matern32": 1, "matern52": 2, "rbf": 3,
                 "piecewise0": 4, "piecewise1": 5, "piecewise2": 6, "piecewise3": 7, "rq": 8,
                 "linear": 9, "poly1": 10, "poly2": 11, "poly3": 12, "poly4": 13, "periodic": 14, "rff": 15}  # enum bbh_kernel_kind
@@ -160,6 +166,17 @@ SIGNATURES = {
         [C.c_void_p, C.c_int32, C.POINTER(ObjectiveProg), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, c_double_p,
          c_double_p, c_double_p, C.c_int64, C.c_double, C.c_double, C.c_void_p, C.c_void_p],
     ),
+    "bbh_desirability_q1": (
+        C.c_int,
+        [C.c_void_p, C.c_int32, C.POINTER(Desirability), C.c_void_p, C.c_void_p, C.c_int64, c_double_p, C.c_int64, C.c_double,
+         C.c_double, C.c_void_p, C.c_void_p],
+    ),
+    "bbh_desirability_pending": (
+        C.c_int,
+        [C.c_void_p, C.c_int32, C.POINTER(Desirability), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, c_double_p,
+         c_double_p, c_double_p, C.c_int64, C.c_double, C.c_double, C.c_int32, C.c_void_p, C.c_void_p],
+    ),
+    "bbh_desirability_last_form": (C.c_int, [C.c_void_p]),
     "bbh_analytic_acq": (
         C.c_int,
         [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_int32,

@@ -353,6 +353,7 @@ struct bbh_handle {
   int last_fit_form = -1;         // bbh_last_fit_form (enum bbh_fit_form)
   int last_nei_form = -1;         // bbh_last_nei_form: 1 fused (bbh_score_nei), 2 unfused (bbh_nei_q1)
   int last_linear_form = -1;      // bbh_linear_last_form: 1 register, 2 block (bbh_linear_moments)
+  int last_des_form = -1;         // bbh_desirability_last_form: 0 LDS, 1 workspace (bbh_desirability_pending)
   int64_t nb_ext = 0;             // blocks incl. pending points (mean/cross pass)
   // pending state
   int p = 0;

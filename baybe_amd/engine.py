@@ -834,6 +834,45 @@ class HipGP:
         self._check(rc, "bbh_mc_acq")
         return scores
 
+    def desirability_acq(self, program, kind: str, mean, var, z: np.ndarray, best_f: float = 0.0, beta: float = 0.2, alive=None,
+                         cross=None, stats=None, form: int = -1):
+        """MC acquisition values (qLogEI ... qPSTD) of N t-batches under a desirability objective with one model per target
+        (``baybe_amd.desirability.DesirabilityProgram``): ``mean`` / ``var`` [T, N] device tensors, ``z`` [S, T]; with pending points
+        ``cross`` [T, N, p], ``stats`` = (mean_p [T, p], cov_pp [T, p, p]) and ``z`` [S, 1 + p, T].  ``form``: storage of the joint
+        factors (0 LDS, 1 workspace, -1 LDS where it fits)."""
+        torch = self._torch()
+        T, N = mean.shape
+        if T != program.n_targets or var.shape != mean.shape or not mean.is_contiguous() or not var.is_contiguous():
+            raise ValueError("mean and var must be contiguous [T, N] tensors, one row per target")
+        z = np.ascontiguousarray(z, dtype=np.float64)
+        scores = torch.empty(N, dtype=torch.float64, device=mean.device)
+        k = _lib.ACQ_KINDS[kind]
+        al = alive.data_ptr() if alive is not None else None
+        des = program.to_struct()
+        if cross is None:
+            if z.ndim != 2 or z.shape[1] != T:
+                raise ValueError("z must be [S, T]")
+            rc = self._lib.bbh_desirability_q1(self._h, k, C.byref(des), mean.data_ptr(), var.data_ptr(), N, _dp(z), z.shape[0],
+                                               float(best_f), float(beta), al, scores.data_ptr())
+        else:
+            if stats is None:
+                raise ValueError("pass stats=(mean_p [T, p], cov_pp [T, p, p]) with cross")
+            mp, cpp = (np.ascontiguousarray(a, dtype=np.float64) for a in stats)
+            p = mp.shape[1]
+            if (not 1 <= p <= MAX_PENDING or tuple(cross.shape) != (T, N, p) or not cross.is_contiguous() or mp.shape != (T, p)
+                    or cpp.shape != (T, p, p) or z.shape[1:] != (p + 1, T)):
+                raise ValueError(f"a desirability objective is scored jointly with 1 ... {MAX_PENDING} pending points: cross [T, N, p], "
+                                 f"stats ([T, p], [T, p, p]), z [S, p + 1, T]")
+            rc = self._lib.bbh_desirability_pending(self._h, k, C.byref(des), mean.data_ptr(), var.data_ptr(), cross.data_ptr(), N, p,
+                                                    _dp(mp), _dp(cpp), _dp(z), z.shape[0], float(best_f), float(beta), int(form), al,
+                                                    scores.data_ptr())
+        self._check(rc, "bbh_desirability")
+        return scores
+
+    def desirability_last_form(self) -> int:
+        """Storage of the factors in the last joint ``desirability_acq`` launch: 0 LDS, 1 workspace, -1 none yet."""
+        return int(self._lib.bbh_desirability_last_form(self._h))
+
     def analytic_acq(self, kind: str, mean, var, best_f: float = 0.0, sign: float = 1.0, beta: float = 0.2,
                      maximize: bool = True, alive=None):
         """Analytic acquisition values (PM, PSTD, UCB, EI, LogEI, PI) of N single candidates."""

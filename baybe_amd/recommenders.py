@@ -95,24 +95,28 @@ def _is_multi_output(objective) -> bool:
     return bool(flag) if flag is not None else len(objective.targets) > 1
 
 
-def _check_objective(objective, acqf):
+def _check_objective(objective, acqf, desirability: str = "refuse"):
     """What of ``baybe.objectives`` is on the device path, checked before anything is fitted: single targets, with their
     transformation as an objective program (``baybe_amd.objective``), and Pareto stacking of identity / negated targets (SURVEY.md
     §8a row a9).  A ``DesirabilityObjective`` is single-output in the reference (scalarised, optimised with qLogEI,
     ``objectives/desirability.py:222-265``) - treating it as Pareto because it has several targets would answer a different
-    question.  Returns the single target's ``ObjectiveProgram`` (None: identity, on the kernels' ``sign`` path)."""
+    question.  Returns the single target's ``ObjectiveProgram`` (None: identity, on the kernels' ``sign`` path) - or, for a
+    desirability objective with one model per target under ``desirability="device"``, its ``DesirabilityProgram``."""
     kind = type(objective).__name__
     from baybe_amd.objective import objective_program
     from baybe_amd.surrogates import _target_sign, modeled_quantities
 
     quantities = modeled_quantities(objective)
     if len(quantities) > 1 and not _is_multi_output(objective):
-        # one model per target + a per-sample scalarisation objective (objectives/desirability.py:229-265): not a device path
-        raise IncompatibilityError(
-            f"Objectives of type '{kind}' scalarise several modeled targets per posterior sample; the HIP path supports "
-            f"single-target and Pareto objectives and 'DesirabilityObjective(as_pre_transformation=True)', which scalarises the "
-            f"measurements before fitting. Use BotorchRecommender otherwise."
-        )
+        # one model per target + a per-sample scalarisation objective (objectives/desirability.py:229-265)
+        if desirability != "device":
+            raise IncompatibilityError(
+                f"Objectives of type '{kind}' scalarise several modeled targets per posterior sample; the HIP path supports "
+                f"single-target and Pareto objectives and 'DesirabilityObjective(as_pre_transformation=True)', which scalarises the "
+                f"measurements before fitting. Use BotorchRecommender otherwise, or pass desirability='device' to the recommender "
+                f"to score the per-sample scalarisation on the device."
+            )
+        return _check_desirability(objective, acqf)
     if _is_multi_output(objective) and not acqf.supports_multi_output:
         raise IncompatibleAcquisitionFunctionError(
             f"You attempted to use a single-output acquisition function in a "
@@ -136,6 +140,38 @@ def _check_objective(objective, acqf):
             f"non-Gaussian outcomes."
         )
     return program
+
+
+def _check_desirability(objective, acqf):
+    """The ``DesirabilityProgram`` of a desirability objective with one model per target, or why the acquisition function does not
+    take it - before anything is fitted."""
+    from baybe_amd.desirability import desirability_program
+
+    kind = type(objective).__name__
+    program = desirability_program(objective)  # raises IncompatibilityError: target count, transformations the kernels do not evaluate
+    if acqf.supports_multi_output:
+        raise IncompatibleAcquisitionFunctionError(
+            f"The acquisition function '{type(acqf).__name__}' needs a multi-output objective, but '{kind}' is a single-output "
+            f"objective; use qLogExpectedImprovement (the default) or another single-output acquisition function."
+        )
+    if getattr(acqf, "kind", None) in ("qNEI", "qLogNEI"):
+        raise IncompatibilityError(
+            f"'{type(acqf).__name__}' under a per-sample desirability scalarisation is not on the HIP path; use "
+            f"qLogExpectedImprovement, qExpectedImprovement, qProbabilityOfImprovement, qSimpleRegret, qUpperConfidenceBound or "
+            f"qPosteriorStandardDeviation, or BotorchRecommender."
+        )
+    if getattr(acqf, "is_analytic", False) and program.as_affine() is None:
+        # Gaussian only for an arithmetic mean of affine targets (to_botorch_posterior_transform, objectives/desirability.py:266-320)
+        raise IncompatibilityError(
+            f"The selected analytical acquisition function '{type(acqf).__name__}' is incompatible with the assigned objective "
+            f"'{kind}' because the former requires a Gaussian distribution and the latter is configured to produce "
+            f"non-Gaussian outcomes."
+        )
+    return program
+
+
+def _is_desirability(program) -> bool:
+    return type(program).__name__ == "DesirabilityProgram"
 
 
 def _check_continuous_part(cont, optimizer: str = "compass") -> None:
@@ -247,7 +283,10 @@ class HipRecommenderImpl:
         return convert_acqf(chosen)
 
     def get_surrogate(self, searchspace, objective, measurements):
-        if _is_multi_output(objective) and not self._surrogate_model.supports_multi_output:
+        from baybe_amd.surrogates import modeled_quantities
+
+        several = _is_multi_output(objective) or len(modeled_quantities(objective)) > 1  # (desirability: one model per target)
+        if several and not self._surrogate_model.supports_multi_output:
             self._surrogate_model = self._surrogate_model.replicate()  # pure/bayesian/base.py:35-39
         self._surrogate_model.fit(searchspace, objective, measurements)
         if self.shard is not None and self.shard.world > 1:
@@ -278,7 +317,16 @@ class HipRecommenderImpl:
             _check_continuous_part(cont, self.continuous_optimizer)  # hybrid / continuous spaces: box-bounded continuous parameters only
         self._objective = objective
         acqf = self._get_acquisition_function(objective, acquisition_function)
-        self._program = _check_objective(objective, acqf)
+        self._program = _check_objective(objective, acqf, self.desirability)
+        if _is_desirability(self._program):  # (before anything is fitted)
+            if cont is not None and not getattr(cont, "is_empty", True):
+                raise IncompatibilityError(
+                    "Desirability objectives with one model per target are scored over discrete search spaces on the HIP path, not "
+                    "hybrid / continuous ones; use 'DesirabilityObjective(as_pre_transformation=True)' or BotorchRecommender.")
+            if self.shard is not None:
+                raise IncompatibilityError(
+                    "Row shards are not on the HIP path of desirability objectives with one model per target; score them on one "
+                    "device, or use 'DesirabilityObjective(as_pre_transformation=True)'.")
         self._acqf_in_use = acqf
         if pending_experiments is not None and not acqf.supports_pending_experiments:
             raise IncompatibleAcquisitionFunctionError(
@@ -290,7 +338,18 @@ class HipRecommenderImpl:
             pend = searchspace.transform(pending_experiments, allow_extra=True)  # _builder.py:326-334
             self._pending_comp = np.ascontiguousarray(pend.to_numpy(dtype=np.float64))
         self._nehvi = None
-        if _is_multi_output(objective):
+        if _is_desirability(self._program):
+            from baybe_amd.desirability import HipDesirability
+
+            # the incumbent is the desirability of the models' means at ALL measurement rows (_builder.py:141-161, 256-265)
+            X_all = np.ascontiguousarray(searchspace.transform(measurements, allow_extra=True).to_numpy(dtype=np.float64))
+            engines = [m.engine for m in surrogate.models]
+            scorer = HipDesirability(engines, self._program, X_all, acqf.kind, getattr(acqf, "n_mc_samples", 512),
+                                     getattr(acqf, "beta", 0.2), device=engines[0].device)
+            self._best_f = scorer.best_f()
+            if not acqf.is_analytic:  # (analytic functions read the combined Gaussian moments: ``_desirability_moments``)
+                self._nehvi = scorer
+        elif _is_multi_output(objective):
             models = surrogate.models
             signs = np.array([m.sign for m in models])
             X_base = np.ascontiguousarray(searchspace.transform(measurements, allow_extra=True).to_numpy(dtype=np.float64))
@@ -486,7 +545,7 @@ class HipRecommenderImpl:
             raise NotImplementedError("Recommenders of type 'BayesianRecommender' do not support empty training data.")
         self._acqf_in_use = self._get_acquisition_function(objective)
         self._pending_comp = None
-        self._program = _check_objective(objective, self._acqf_in_use)  # (decides the batch-size cap)
+        self._program = _check_objective(objective, self._acqf_in_use, self.desirability)  # (decides the batch-size cap)
         self._check_batch_size(batch_size, pending_experiments)  # before the fit
         self._setup_botorch_acqf(searchspace, objective, measurements, pending_experiments)
         return self._recommend_with_discrete_parts(searchspace, batch_size, pending_experiments=pending_experiments)
@@ -600,6 +659,11 @@ class HipRecommenderImpl:
         surrogate = self._surrogate_model
         acqf = self._acqf_in_use
         Xd, alive, labels = self._candidates_on_device(subspace_discrete, candidates_exp, keep_mask)
+        if self._nehvi is not None and _is_desirability(self._program):
+            # the desirability scorer: ONE sampler seed per recommendation, as on the single-target path
+            res = self._nehvi.greedy(Xd, batch_size, seed=self._sampler_seed(), X_pending=self._pending_comp, alive=alive)
+            idxs = labels[np.asarray(res.indices, dtype=np.int64)]
+            return (idxs, res) if return_values else idxs
         if self._nehvi is not None and (getattr(surrogate, "is_ensemble", False) or getattr(surrogate, "is_independent_gaussian", False)):
             # the forest / linear scorer: ONE sampler seed per recommendation (their posteriors have no pruning draw)
             res = self._nehvi.greedy(Xd, batch_size, seed=self._sampler_seed(), X_pending=self._pending_comp, alive=alive)
@@ -611,8 +675,11 @@ class HipRecommenderImpl:
             idxs = labels[np.asarray(res.indices, dtype=np.int64)]
             return (idxs, res) if return_values else idxs
         if acqf.is_analytic:  # q = 1 by construction (supports_batching is False)
-            eng = surrogate.engine
-            mean, var = eng.posterior(Xd)
+            if _is_desirability(self._program):
+                eng, mean, var = self._desirability_moments(Xd)
+            else:
+                eng = surrogate.engine
+                mean, var = eng.posterior(Xd)
             scores = self._analytic_scores(eng, acqf, mean, var, self._sign(surrogate), alive)
             val, idx = eng.argmax(scores)
             if self.shard is not None:
@@ -845,7 +912,22 @@ class HipRecommenderImpl:
         i = int(np.argmax(val))
         return cur[i], float(val[i])
 
+    def _desirability_moments(self, X):
+        """(first engine, mean, var) of the Gaussian desirability N(sum_t c_t mu_t + offset, sum_t c_t^2 sigma_t^2) of an arithmetic
+        mean of affine targets (``DesirabilityProgram.as_affine``; to_botorch_posterior_transform, objectives/desirability.py:266-320)."""
+        c, offset = self._program.as_affine()
+        engines = [m.engine for m in self._surrogate_model.models]
+        mean = var = None
+        for ct, e in zip(c, engines):
+            m, v = e.posterior(X)
+            mean = ct * m + offset if mean is None else mean + ct * m
+            var = (ct * ct) * v if var is None else var + (ct * ct) * v
+        return engines[0], mean, var
+
     def _analytic_scores(self, eng, acqf, mean, var, sign, alive=None):
+        if _is_desirability(self._program):  # (the moments are the desirability's already)
+            return eng.analytic_acq(acqf.kind, mean, var, self._best_f, 1.0, getattr(acqf, "beta", 0.2),
+                                    getattr(acqf, "maximize", True), alive)
         if self._program is not None:
             # an affine objective is the reference's posterior transform (objectives/single.py:77-91): N(a mu + b, a^2 sigma^2)
             a, b = self._program.as_affine()
@@ -861,6 +943,15 @@ class HipRecommenderImpl:
             from baybe_amd.linear import JOINT_TEXT
 
             raise IncompatibleSurrogateError(f"'{type(self._surrogate_model).__name__}' {JOINT_TEXT}.")
+        if _is_desirability(self._program):
+            if self._nehvi is None:  # analytic: single points only
+                if len(comp) != 1 or self._pending_comp is not None:
+                    raise IncompatibleAcquisitionFunctionError("Analytic acquisition functions score single points only.")
+                eng, mean, var = self._desirability_moments(comp)
+                return float(self._analytic_scores(eng, self._acqf_in_use, mean, var, 1.0).cpu().numpy()[0])
+            base = self._pending_comp if self._pending_comp is not None else np.zeros((0, comp.shape[1]))
+            sc = self._nehvi.score(comp[:1], X_pending=np.vstack([comp[1:], base]), seed=self._sampler_seed())
+            return float(sc.cpu().numpy()[0])
         if self._nehvi is not None:
             # incremental NEHVI: the batch value is the value of its last point given the others
             self._nehvi.prepare(self._sampler_seed(), np.vstack([comp[:-1]] + ([self._pending_comp] if self._pending_comp is not None else [])) if len(comp) > 1 or self._pending_comp is not None else None)
@@ -916,6 +1007,12 @@ class HipRecommenderImpl:
         """``BayesianRecommender.acquisition_values`` (base.py:199-238): one value per candidate."""
         surrogate, acqf = self._setup_acqf(searchspace, objective, measurements, pending_experiments, acquisition_function)
         comp = np.ascontiguousarray(searchspace.transform(candidates, allow_extra=True).to_numpy(dtype=np.float64))
+        if _is_desirability(self._program):
+            if self._nehvi is None:
+                eng, mean, var = self._desirability_moments(comp)
+                return pd.Series(self._analytic_scores(eng, acqf, mean, var, 1.0).cpu().numpy(), index=candidates.index)
+            sc = self._nehvi.score(comp, X_pending=self._pending_comp, seed=self._sampler_seed())
+            return pd.Series(sc.cpu().numpy(), index=candidates.index)
         if self._nehvi is not None:
             self._nehvi.prepare(self._sampler_seed(), self._pending_comp)
             sc = self._nehvi.score(self._nehvi.outputs[0].engine._as_dev(comp))
@@ -956,6 +1053,15 @@ def _convert_continuous_optimizer(value):
     return name
 
 
+def _convert_desirability(value):
+    """What happens to a ``DesirabilityObjective`` with one model per target (its default): "refuse" names the alternatives,
+    "device" scores the per-sample scalarisation on the device (``baybe_amd.desirability``)."""
+    name = str(getattr(value, "value", value))
+    if name not in ("refuse", "device"):
+        raise ValueError(f"'{value}' is not a valid desirability setting (refuse, device)")
+    return name
+
+
 def _validate_percentage(_, attribute, value):
     if not 0 <= value <= 1:  # botorch/core.py:123-135
         raise ValueError(f"Hybrid sampling percentage needs to be between 0 and 1 but is {value}")
@@ -978,6 +1084,8 @@ def recommender_fields(with_base_fields: bool = True, surrogate_factory=HipGauss
         "n_raw_samples": field(default=64, validator=[instance_of(int), gt(0)], kw_only=True),
         # refinement of the continuous coordinates: the pattern search, or - opt-in - gradient ascent on device-side derivatives
         "continuous_optimizer": field(default="compass", converter=_convert_continuous_optimizer, kw_only=True),
+        # DesirabilityObjective with one model per target: refused (naming the alternatives), or - opt-in - scored per sample on the device
+        "desirability": field(default="refuse", converter=_convert_desirability, kw_only=True),
         # optional baybe_amd.distributed.RowShard: this process scores only its row range and joins one all-gather
         # per selection step (multi-GPU)
         "shard": field(default=None, eq=False, repr=False, kw_only=True),
@@ -986,7 +1094,7 @@ def recommender_fields(with_base_fields: bool = True, surrogate_factory=HipGauss
         "_cand_cache": field(default=None, init=False, eq=False, repr=False),
         "_nehvi": field(default=None, init=False, eq=False, repr=False),
         "_acqf_in_use": field(default=None, init=False, eq=False, repr=False),
-        "_program": field(default=None, init=False, eq=False, repr=False),  # ObjectiveProgram of a transformed single target
+        "_program": field(default=None, init=False, eq=False, repr=False),  # ObjectiveProgram of a transformed single target, or a DesirabilityProgram
         # per greedy step of the last hybrid / continuous recommendation under "gradient": starts, final points, values (tests, timing)
         "_last_continuous_trace": field(default=None, init=False, eq=False, repr=False),
     }

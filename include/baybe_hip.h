@@ -325,6 +325,33 @@ int bbh_mc_acq_obj_pending(bbh_handle* h, int32_t kind, const bbh_objective_prog
                            const double* var_dev, const double* cross_dev, int64_t N, int64_t p, const double* mean_p_host,
                            const double* cov_pp_host, const double* z_host, int64_t S, double best_f, double beta,
                            const uint8_t* alive_dev, double* scores_dev);
+
+/* ---- desirability objectives with one model per target (bbh_desirability.hip) ----------------------------------------------
+ * baybe/objectives/desirability.py:229-264 (as_pre_transformation=False, the default): every target has its own surrogate and the
+ * desirability is computed per posterior sample, d = scal_t(w_t, prog_t(y_t)), in front of the acquisition utility.
+ * BBH_SCAL_MEAN: sum_t w_t g_t;  BBH_SCAL_GEOM_MEAN: exp(sum_t w_t log(g_t + 2^-52)); both in ascending t with rounded products. */
+enum bbh_scalarizer { BBH_SCAL_MEAN = 0, BBH_SCAL_GEOM_MEAN = 1 };
+#define BBH_DES_MAX_TARGETS 8
+typedef struct bbh_desirability {
+  int32_t n_targets, scalarizer; /* 2 ... BBH_DES_MAX_TARGETS targets */
+  double weight[BBH_DES_MAX_TARGETS];
+  bbh_objective_prog prog[BBH_DES_MAX_TARGETS];
+} bbh_desirability;
+/* t-batches of one point: mean_dev / var_dev [T, N] (target-major), z_host [S, T]; kind BBH_ACQ_QLOGEI ... BBH_ACQ_QPSTD;
+ * 1 <= S <= 8192.  -inf for a masked row. */
+int bbh_desirability_q1(bbh_handle* h, int32_t kind, const bbh_desirability* des, const double* mean_dev, const double* var_dev,
+                        int64_t N, const double* z_host, int64_t S, double best_f, double beta, const uint8_t* alive_dev,
+                        double* scores_dev);
+/* t-batches [x_i ; pending], 1 <= p <= 15: cross_dev [T, N, p], mean_p_host [T, p], cov_pp_host [T, p, p], z_host [S, p + 1, T].
+ * form: where the T thread-private Cholesky factors live - 0 LDS (bad arguments where they do not fit the workgroup's LDS, nothing
+ * is launched), 1 a chunked global workspace, -1 LDS where it fits; both forms give the same bits.  -inf for a masked row, NaN for
+ * a row of which ANY target's joint covariance does not factor at any jitter level. */
+int bbh_desirability_pending(bbh_handle* h, int32_t kind, const bbh_desirability* des, const double* mean_dev, const double* var_dev,
+                             const double* cross_dev, int64_t N, int64_t p, const double* mean_p_host, const double* cov_pp_host,
+                             const double* z_host, int64_t S, double best_f, double beta, int32_t form, const uint8_t* alive_dev,
+                             double* scores_dev);
+int bbh_desirability_last_form(bbh_handle* h); /* of the last bbh_desirability_pending launch: 0 LDS, 1 workspace, -1 none yet */
+
 /* Analytic family (q = 1): PM, PSTD(+-), UCB(beta), EI, LogEI, PI; sigma^2 clamped at 1e-12. */
 int bbh_analytic_acq(bbh_handle* h, int32_t kind, const double* mean_dev, const double* var_dev, int64_t N,
                      double best_f, double sign, double beta, int32_t maximize, const uint8_t* alive_dev,
