@@ -64,6 +64,7 @@ MAX_PENDING = 15  # pending points per cross-covariance pass / in the handle's p
 MAX_PENDING_BIG = 63  # joint q'-batches through bbh_qlogei_pending_big: q' = 1 + pending <= 64 (qLogEI)
 MAX_RFF_SAMPLES = 256  # RFFKernel(num_samples): frequencies of the feature-space model (csrc/bbh_rff.hip: m = 2 D <= 512)
 MAX_OBJECTIVES = 4
+EHVI_MAX_Q = 8  # joint q'-batches of qEHVI / qLogEHVI: q' = 1 + pending <= 8, 255 subsets (BBH_EHVI_MAX_Q)
 TIMED_FAMILIES = {"posterior": 0, "cross": 1, "pending": 2, "columns": 3, "nehvi": 4, "q1": 5, "select": 6}  # enum bbh_timed_family
 ACQ_KINDS = {"qLogEI": 0, "qEI": 1, "qPI": 2, "qSR": 3, "qUCB": 4, "qPSTD": 5, "qNEI": 6, "qLogNEI": 7,
              "PM": 10, "PSTD": 11, "UCB": 12, "EI": 13, "LogEI": 14, "PI": 15}
@@ -177,6 +178,17 @@ SIGNATURES = {
          c_double_p, c_double_p, C.c_int64, C.c_double, C.c_double, C.c_int32, C.c_void_p, C.c_void_p],
     ),
     "bbh_desirability_last_form": (C.c_int, [C.c_void_p]),
+    "bbh_ehvi_q1": (
+        C.c_int,
+        [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, c_double_p, c_double_p, C.c_int64, c_double_p, C.c_int64,
+         C.c_void_p, C.c_void_p],
+    ),
+    "bbh_ehvi_pending": (
+        C.c_int,
+        [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, c_double_p, c_double_p, c_double_p,
+         c_double_p, C.c_int64, c_double_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p],
+    ),
+    "bbh_ehvi_last_form": (C.c_int, [C.c_void_p]),
     "bbh_analytic_acq": (
         C.c_int,
         [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_int32,

@@ -2,7 +2,7 @@
 
 Only what the hot path scores on the device is defined: qLogEI (``acqfs.py:219-223``), the noisy forms qNEI / qLogNEI
 (``acqfs.py:226-243``), the noisy Pareto functions qLogNEHVI / qNEHVI (``acqfs.py:467-484``) and qLogNParEGO
-(``acqfs.py:328-336``), and the closed-form/posterior read-backs built from (mean, variance).  BoTorch's defaults that BayBE
+(``acqfs.py:328-336``), the non-noisy pair qEHVI / qLogEHVI (``acqfs.py:429-464``; opt-in, ``ehvi="device"``), and the closed-form/posterior read-backs built from (mean, variance).  BoTorch's defaults that BayBE
 does not expose are recorded as explicit fields (sample count 512; fat=True, tau_relu=1e-6,
 tau_max=1e-2 are compiled into the kernels)."""
 
@@ -148,6 +148,38 @@ class qNoisyExpectedHypervolumeImprovement:
 qNEHVI = qNoisyExpectedHypervolumeImprovement
 
 
+def _convert_alpha(value):
+    return None if value is None else float(value)
+
+
+def _ehvi_class(name: str, abbr: str, doc: str):
+    """Declarative (non-noisy) expected hypervolume improvement (``acqfs.py:429-464``), scored by ``baybe_amd.ehvi.HipEHVI`` under
+    the recommender's ``ehvi="device"``.  There is no ``prune_baseline``: nothing is sampled at the measurement rows."""
+    ns = {
+        "__doc__": doc, "abbreviation": abbr, "kind": abbr, "supports_batching": True, "supports_pending_experiments": True,
+        "supports_multi_output": True, "is_mc": True, "is_analytic": False,
+        "__annotations__": {"abbreviation": ClassVar[str], "kind": ClassVar[str], "supports_batching": ClassVar[bool],
+                            "supports_pending_experiments": ClassVar[bool], "supports_multi_output": ClassVar[bool],
+                            "is_mc": ClassVar[bool], "is_analytic": ClassVar[bool], "n_mc_samples": int},
+        # None: computed from the measured targets; float: the factor of ``compute_ref_point``; iterable: the coordinates
+        "reference_point": field(default=None, converter=_convert_ref),
+        # threshold of the partitioning: None (BoTorch's default, 0 for up to 4 objectives) and 0 are the exact partitioning; a positive
+        # value asks for the approximate one, which the recommender refuses
+        "alpha": field(default=None, converter=_convert_alpha),
+        # Sobol base samples (BoTorch default for multi-objective MC acquisition functions)
+        "n_mc_samples": field(default=128, validator=[instance_of(int), ge(1)]),
+    }
+    return define(frozen=True)(type(name, (), ns))
+
+
+qExpectedHypervolumeImprovement = _ehvi_class("qExpectedHypervolumeImprovement", "qEHVI",
+                                              "Monte Carlo based expected hypervolume improvement.")
+qLogExpectedHypervolumeImprovement = _ehvi_class("qLogExpectedHypervolumeImprovement", "qLogEHVI",
+                                                 "Logarithmic Monte Carlo based expected hypervolume improvement.")
+qEHVI, qLogEHVI = qExpectedHypervolumeImprovement, qLogExpectedHypervolumeImprovement
+_EHVI = {c.abbreviation: c for c in (qExpectedHypervolumeImprovement, qLogExpectedHypervolumeImprovement)}
+
+
 def _convert_weights(value):
     return None if value is None else tuple(float(v) for v in value)
 
@@ -207,8 +239,26 @@ qNEI, qLogNEI = qNoisyExpectedImprovement, qLogNoisyExpectedImprovement
 _NOISY_EI = {c.abbreviation: c for c in (qNoisyExpectedImprovement, qLogNoisyExpectedImprovement)}
 
 
-def convert_acqf(acqf):
-    """``baybe.acquisition.utils.convert_acqf``: accept abbreviations / BayBE objects."""
+def convert_acqf(acqf, ehvi: str = "refuse"):
+    """``baybe.acquisition.utils.convert_acqf``: accept abbreviations / BayBE objects.  ``ehvi``: the recommender's setting of that
+    name - "device" converts qEHVI / qLogEHVI (abbreviations, full names, our instances, the reference's objects by class name),
+    "refuse" refuses them and names the setting."""
+    name = acqf if isinstance(acqf, str) else type(acqf).__name__
+    for abbr, cls in _EHVI.items():
+        if name in (abbr, cls.__name__):
+            if ehvi != "device":
+                from baybe_amd.exceptions import IncompatibleAcquisitionFunctionError
+
+                raise IncompatibleAcquisitionFunctionError(
+                    f"The HIP recommender scores the MC / analytic EI-PI-UCB-SR families, qNEI / qLogNEI, qLogNEHVI / qNEHVI and "
+                    f"qLogNParEGO on the device; '{name}' is not available on this path. Pass ehvi='device' to the recommender to "
+                    f"score qEHVI / qLogEHVI on the device by joint q-batch inclusion-exclusion."
+                )
+            if isinstance(acqf, cls):
+                return acqf
+            if isinstance(acqf, str):
+                return cls()
+            return cls(reference_point=getattr(acqf, "reference_point", None), alpha=getattr(acqf, "alpha", None))
     if acqf is None or isinstance(acqf, (qLogExpectedImprovement, *_NOISY_PARETO.values())):
         return acqf
     if type(acqf) in _SINGLE_OUTPUT.values() or type(acqf) in _NOISY_EI.values():

@@ -46,6 +46,7 @@ static bbh_switches bbh_read_switches() {
       {"BBH_NEHVI_LOG", IS, '1', &S::nehvi_log, nullptr},
       {"BBH_NEHVI_SLICES", INT, 0, nullptr, &S::nehvi_slices},
       {"BBH_NEHVI_PK", NOT, '0', &S::nehvi_pk, nullptr},
+      {"BBH_EHVI_SLICE", INT, 0, nullptr, &S::ehvi_slice},
       {"BBH_NEI_FUSED", NOT, '0', &S::nei_fused, nullptr},
       {"BBH_SELECT", NOT, '0', &S::select_on, nullptr},
       {"BBH_SELECT_MAPPED", NOT, '0', &S::select_mapped, nullptr},

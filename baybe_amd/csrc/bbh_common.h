@@ -216,6 +216,7 @@ struct bbh_switches {
   bool nehvi_log = false;         // BBH_NEHVI_LOG=1: log-domain sums of qLogNEHVI instead of the linear-domain ones
   int nehvi_slices = INT_MIN;     // BBH_NEHVI_SLICES: sample slices of the linear-domain qLogNEHVI kernel (unset: by size)
   bool nehvi_pk = true;           // BBH_NEHVI_PK=0: double-precision fat-minimum factors in the linear-domain qLogNEHVI kernel (A/B)
+  int ehvi_slice = INT_MIN;       // BBH_EHVI_SLICE: MC samples per slice of the qEHVI / qLogEHVI kernels, 0 = all in one slice (unset: 16; A/B)
   bool nei_fused = true;          // BBH_NEI_FUSED=0: qNEI / qLogNEI through bbh_posterior_columns_sm + bbh_nei_q1 instead of the fused scoring pass (A/B, verification)
   bool select_on = true;          // BBH_SELECT=0: top-k / argmax by k rounds of workgroup argmax (A/B)
   bool select_mapped = true;      // BBH_SELECT_MAPPED=0: selection results through a device buffer + copy instead of host-mapped stores (A/B)
@@ -354,6 +355,7 @@ struct bbh_handle {
   int last_nei_form = -1;         // bbh_last_nei_form: 1 fused (bbh_score_nei), 2 unfused (bbh_nei_q1)
   int last_linear_form = -1;      // bbh_linear_last_form: 1 register, 2 block (bbh_linear_moments)
   int last_des_form = -1;         // bbh_desirability_last_form: 0 LDS, 1 workspace (bbh_desirability_pending)
+  int last_ehvi_form = -1;        // bbh_ehvi_last_form: 0 LDS, 1 workspace (bbh_ehvi_pending)
   int64_t nb_ext = 0;             // blocks incl. pending points (mean/cross pass)
   // pending state
   int p = 0;

@@ -873,6 +873,45 @@ class HipGP:
         """Storage of the factors in the last joint ``desirability_acq`` launch: 0 LDS, 1 workspace, -1 none yet."""
         return int(self._lib.bbh_desirability_last_form(self._h))
 
+    def ehvi_acq(self, log: bool, mean, var, cells, z: np.ndarray, alive=None, cross=None, stats=None, form: int = -1):
+        """qEHVI (``log=False``) / qLogEHVI values of N t-batches against one fixed cell list (``acqfs.py:429-464``): ``mean`` / ``var``
+        [m, N] device tensors, ``cells`` = (lower [C, m], upper [C, m]; upper bounds may be +inf), ``z`` [S, m]; with pending points
+        ``cross`` [m, N, p], ``stats`` = (mean_p [m, p], cov_pp [m, p, p]) and ``z`` [S, 1 + p, m].  Everything ORIENTED: the caller
+        has negated the means and the base-sample columns of minimised targets.  ``form``: storage of the joint factors (0 LDS,
+        1 workspace, -1 the library's choice: the workspace, which measured faster)."""
+        torch = self._torch()
+        m, N = mean.shape
+        if var.shape != mean.shape or not mean.is_contiguous() or not var.is_contiguous():
+            raise ValueError("mean and var must be contiguous [m, N] tensors, one row per target")
+        lo, up = (np.ascontiguousarray(a, dtype=np.float64) for a in cells)
+        if lo.ndim != 2 or lo.shape[1] != m or up.shape != lo.shape:
+            raise ValueError("cells must be (lower [C, m], upper [C, m])")
+        z = np.ascontiguousarray(z, dtype=np.float64)
+        scores = torch.empty(N, dtype=torch.float64, device=mean.device)
+        al = alive.data_ptr() if alive is not None else None
+        if cross is None:
+            if z.ndim != 2 or z.shape[1] != m:
+                raise ValueError("z must be [S, m]")
+            rc = self._lib.bbh_ehvi_q1(self._h, int(bool(log)), m, mean.data_ptr(), var.data_ptr(), N, _dp(lo), _dp(up), lo.shape[0], _dp(z),
+                                       z.shape[0], al, scores.data_ptr())
+        else:
+            if stats is None:
+                raise ValueError("pass stats=(mean_p [m, p], cov_pp [m, p, p]) with cross")
+            mp, cpp = (np.ascontiguousarray(a, dtype=np.float64) for a in stats)
+            p = mp.shape[1]
+            if (cross.dim() != 3 or tuple(cross.shape) != (m, N, p) or not cross.is_contiguous() or mp.shape != (m, p)
+                    or cpp.shape != (m, p, p) or z.ndim != 3 or z.shape[1:] != (p + 1, m)):
+                raise ValueError("a hypervolume improvement is scored jointly with cross [m, N, p], stats ([m, p], [m, p, p]), "
+                                 "z [S, p + 1, m]")
+            rc = self._lib.bbh_ehvi_pending(self._h, int(bool(log)), m, mean.data_ptr(), var.data_ptr(), cross.data_ptr(), N, p, _dp(mp),
+                                            _dp(cpp), _dp(lo), _dp(up), lo.shape[0], _dp(z), z.shape[0], int(form), al, scores.data_ptr())
+        self._check(rc, "bbh_ehvi")
+        return scores
+
+    def ehvi_last_form(self) -> int:
+        """Storage of the factors in the last joint ``ehvi_acq`` launch: 0 LDS, 1 workspace, -1 none yet."""
+        return int(self._lib.bbh_ehvi_last_form(self._h))
+
     def analytic_acq(self, kind: str, mean, var, best_f: float = 0.0, sign: float = 1.0, beta: float = 0.2,
                      maximize: bool = True, alive=None):
         """Analytic acquisition values (PM, PSTD, UCB, EI, LogEI, PI) of N single candidates."""

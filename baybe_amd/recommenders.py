@@ -174,6 +174,11 @@ def _is_desirability(program) -> bool:
     return type(program).__name__ == "DesirabilityProgram"
 
 
+def _is_ehvi(acqf) -> bool:
+    """qEHVI / qLogEHVI: scored by ``baybe_amd.ehvi.HipEHVI`` (joint q'-batches), not by the baseline-caching noisy scorers."""
+    return getattr(acqf, "kind", None) in ("qEHVI", "qLogEHVI")
+
+
 def _check_continuous_part(cont, optimizer: str = "compass") -> None:
     """What of ``SubspaceContinuous`` the HIP path's search handles: box-bounded parameters.  Linear / nonlinear / cardinality /
     interpoint constraints need the reference's constrained optimiser.  ``optimizer``: the recommender's ``continuous_optimizer``."""
@@ -280,7 +285,7 @@ class HipRecommenderImpl:
         chosen = override if override is not None else self.acquisition_function
         if chosen is None:
             return qLogNoisyExpectedHypervolumeImprovement() if _is_multi_output(objective) else qLogExpectedImprovement()
-        return convert_acqf(chosen)
+        return convert_acqf(chosen, ehvi=getattr(self, "ehvi", "refuse"))
 
     def get_surrogate(self, searchspace, objective, measurements):
         from baybe_amd.surrogates import modeled_quantities
@@ -327,6 +332,22 @@ class HipRecommenderImpl:
                 raise IncompatibilityError(
                     "Row shards are not on the HIP path of desirability objectives with one model per target; score them on one "
                     "device, or use 'DesirabilityObjective(as_pre_transformation=True)'.")
+        if _is_ehvi(acqf):  # (before anything is fitted)
+            from baybe_amd.ehvi import MAX_OBJECTIVES, check_alpha
+
+            check_alpha(acqf.alpha)
+            if len(objective.targets) > MAX_OBJECTIVES:
+                raise IncompatibilityError(
+                    f"'{type(acqf).__name__}' is scored for 2 to {MAX_OBJECTIVES} targets on the HIP path "
+                    f"({len(objective.targets)} given). Use BotorchRecommender.")
+            if cont is not None and not getattr(cont, "is_empty", True):
+                raise IncompatibilityError(
+                    f"'{type(acqf).__name__}' is scored over discrete search spaces on the HIP path, not hybrid / continuous ones; "
+                    f"use BotorchRecommender.")
+            if self.shard is not None:
+                raise IncompatibilityError(
+                    f"Row shards are not on the HIP path of '{type(acqf).__name__}'; score the candidates on one device, or use "
+                    f"qLogNoisyExpectedHypervolumeImprovement.")
         self._acqf_in_use = acqf
         if pending_experiments is not None and not acqf.supports_pending_experiments:
             raise IncompatibleAcquisitionFunctionError(
@@ -376,6 +397,15 @@ class HipRecommenderImpl:
                         )
                     kw = {} if ref is None else {"factor": ref}
                     ref = compute_ref_point(complete.to_numpy(dtype=np.float64) * signs[None, :], **kw)
+                if _is_ehvi(acqf):
+                    from baybe_amd.ehvi import HipEHVI
+
+                    # the partitioning comes from the models' posterior means at ALL measurement rows (_builder.py:286-299)
+                    self._nehvi = HipEHVI([m.engine for m in models], signs, X_base, np.asarray(ref, dtype=np.float64),
+                                          log=acqf.kind == "qLogEHVI", n_mc_samples=acqf.n_mc_samples, alpha=acqf.alpha,
+                                          device=models[0].engine.device)
+                    self._best_f = None
+                    return surrogate, acqf
                 scorer = HipNEHVIPlain if acqf.kind == "qNEHVI" else HipNEHVI
                 self._nehvi = scorer([m.engine for m in models], signs, X_base, np.asarray(ref, dtype=np.float64),
                                      n_mc_samples=acqf.n_mc_samples, prune_baseline=acqf.prune_baseline,
@@ -523,6 +553,11 @@ class HipRecommenderImpl:
                 raise IncompatibleSurrogateError(f"'{type(self._surrogate_model).__name__}' {JOINT_TEXT}.")
             return
         acqf = self._acqf_in_use
+        if _is_ehvi(acqf):  # the candidate, the pending experiments and the picks are ONE joint batch (no baseline to cache them into)
+            from baybe_amd.ehvi import HipEHVI
+
+            HipEHVI.check_batch(1 + n_pend + batch_size)
+            return
         if acqf is not None and (acqf.supports_multi_output or getattr(acqf, "is_analytic", False)
                                  or getattr(acqf, "kind", None) in ("qNEI", "qLogNEI")):
             return
@@ -659,8 +694,8 @@ class HipRecommenderImpl:
         surrogate = self._surrogate_model
         acqf = self._acqf_in_use
         Xd, alive, labels = self._candidates_on_device(subspace_discrete, candidates_exp, keep_mask)
-        if self._nehvi is not None and _is_desirability(self._program):
-            # the desirability scorer: ONE sampler seed per recommendation, as on the single-target path
+        if self._nehvi is not None and (_is_desirability(self._program) or _is_ehvi(self._acqf_in_use)):
+            # the desirability / hypervolume-improvement scorers: ONE sampler seed per recommendation, as on the single-target path
             res = self._nehvi.greedy(Xd, batch_size, seed=self._sampler_seed(), X_pending=self._pending_comp, alive=alive)
             idxs = labels[np.asarray(res.indices, dtype=np.int64)]
             return (idxs, res) if return_values else idxs
@@ -952,6 +987,8 @@ class HipRecommenderImpl:
             base = self._pending_comp if self._pending_comp is not None else np.zeros((0, comp.shape[1]))
             sc = self._nehvi.score(comp[:1], X_pending=np.vstack([comp[1:], base]), seed=self._sampler_seed())
             return float(sc.cpu().numpy()[0])
+        if _is_ehvi(self._acqf_in_use):  # one joint q-batch: the batch and the pending experiments
+            return self._nehvi.joint_value(comp, X_pending=self._pending_comp, seed=self._sampler_seed())
         if self._nehvi is not None:
             # incremental NEHVI: the batch value is the value of its last point given the others
             self._nehvi.prepare(self._sampler_seed(), np.vstack([comp[:-1]] + ([self._pending_comp] if self._pending_comp is not None else [])) if len(comp) > 1 or self._pending_comp is not None else None)
@@ -1013,6 +1050,9 @@ class HipRecommenderImpl:
                 return pd.Series(self._analytic_scores(eng, acqf, mean, var, 1.0).cpu().numpy(), index=candidates.index)
             sc = self._nehvi.score(comp, X_pending=self._pending_comp, seed=self._sampler_seed())
             return pd.Series(sc.cpu().numpy(), index=candidates.index)
+        if _is_ehvi(acqf):
+            sc = self._nehvi.score(comp, X_pending=self._pending_comp, seed=self._sampler_seed())
+            return pd.Series(sc.cpu().numpy(), index=candidates.index)
         if self._nehvi is not None:
             self._nehvi.prepare(self._sampler_seed(), self._pending_comp)
             sc = self._nehvi.score(self._nehvi.outputs[0].engine._as_dev(comp))
@@ -1062,6 +1102,19 @@ def _convert_desirability(value):
     return name
 
 
+def _convert_ehvi(value):
+    """What happens to qEHVI / qLogEHVI: "refuse" names the alternatives (and the setting), "device" scores them on the device
+    (``baybe_amd.ehvi``)."""
+    name = str(getattr(value, "value", value))
+    if name not in ("refuse", "device"):
+        raise ValueError(f"'{value}' is not a valid ehvi setting (refuse, device)")
+    return name
+
+
+def _convert_acqf_field(value, self):
+    return convert_acqf(value, ehvi=getattr(self, "ehvi", "refuse"))
+
+
 def _validate_percentage(_, attribute, value):
     if not 0 <= value <= 1:  # botorch/core.py:123-135
         raise ValueError(f"Hybrid sampling percentage needs to be between 0 and 1 but is {value}")
@@ -1086,6 +1139,8 @@ def recommender_fields(with_base_fields: bool = True, surrogate_factory=HipGauss
         "continuous_optimizer": field(default="compass", converter=_convert_continuous_optimizer, kw_only=True),
         # DesirabilityObjective with one model per target: refused (naming the alternatives), or - opt-in - scored per sample on the device
         "desirability": field(default="refuse", converter=_convert_desirability, kw_only=True),
+        # qEHVI / qLogEHVI: refused (naming the setting), or - opt-in - scored on the device by joint q'-batch inclusion-exclusion
+        "ehvi": field(default="refuse", converter=_convert_ehvi, kw_only=True),
         # optional baybe_amd.distributed.RowShard: this process scores only its row range and joins one all-gather
         # per selection step (multi-GPU)
         "shard": field(default=None, eq=False, repr=False, kw_only=True),
@@ -1099,7 +1154,8 @@ def recommender_fields(with_base_fields: bool = True, surrogate_factory=HipGauss
         "_last_continuous_trace": field(default=None, init=False, eq=False, repr=False),
     }
     if with_base_fields:
-        f["acquisition_function"] = field(default=None, converter=convert_acqf, kw_only=True)
+        # (converted under the instance's ``ehvi`` setting, which is declared - and therefore set - before it)
+        f["acquisition_function"] = field(default=None, converter=attrs.Converter(_convert_acqf_field, takes_self=True), kw_only=True)
         f["_objective"] = field(default=None, init=False, eq=False, repr=False)
     return f
 

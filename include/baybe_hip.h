@@ -472,6 +472,35 @@ int bbh_qnehvi_sm(bbh_handle* h, int32_t m, int64_t N, const double* const* tmat
                   const double* sign_host, const double* zx_host, int64_t S, const int64_t* cell_off_host, const double* cell_lo_host,
                   const double* cell_loglen_host, const uint8_t* alive_dev, double* scores_dev);
 
+/* ---- qExpectedHypervolumeImprovement / qLogExpectedHypervolumeImprovement (baybe/acquisition/acqfs.py:429-464) ---------------
+ * The non-noisy pair: ONE cell list per recommendation (the box decomposition of the models' oriented posterior means at the
+ * measurement rows, baybe/acquisition/_builder.py:286-299), cell_lo_host / cell_up_host [C, m] (the upper bounds may be +inf),
+ * C >= 1, 2 <= m <= BBH_MAX_OBJECTIVES.  Every operand arrives ORIENTED: the caller negates the means (and pending means) of a
+ * minimised target and that target's base-sample column, so that y = mean + L z is sign (m + L z); variances and covariances carry
+ * no sign.  The m targets are independent, the q' = 1 + p points of one target jointly Gaussian (bbh_joint.h: psd_safe_cholesky
+ * per target).  Per base sample s and cell c, with y[r, j] the draw of point r and target j:
+ *   log == 0 (qEHVI):    sum over the non-empty subsets A of the q' points of (-1)^(|A|+1) prod_j max(0, min_{r in A}(min(y[r,j], up_c[j]) - lo_c[j]))
+ *   log != 0 (qLogEHVI): li = log_fatplus(y - lo; 1e-6); per subset sum_j fatmin2(fatmin_{r in A} li, log(min(up, 1e10) - lo); 1e-2);
+ *                        logsumexp per subset size, logaddexp into an odd and an even slot, logdiffexp(odd, even) per cell
+ * summed over the cells and averaged over the samples (logsumexp / logmeanexp in the log form).  The subsets are walked by
+ * ascending size, lexicographically within a size; double precision throughout.  The samples are cut into slices of a fixed
+ * length over a second grid dimension and the slices are finished in slice order, so two runs give the same bits.
+ * -inf for a masked row. */
+#define BBH_EHVI_MAX_Q 8 /* q' = 1 + p <= 8: 255 subsets */
+/* q' = 1: mean_dev / var_dev [m, N] (target-major), z_host [S, m]; 1 <= S <= 8192; 1 x 1 jitter as bbh_mc_acq_q1. */
+int bbh_ehvi_q1(bbh_handle* h, int32_t log, int32_t m, const double* mean_dev, const double* var_dev, int64_t N,
+                const double* cell_lo_host, const double* cell_up_host, int64_t C, const double* z_host, int64_t S,
+                const uint8_t* alive_dev, double* scores_dev);
+/* t-batches [x_i ; pending], 1 <= p <= BBH_EHVI_MAX_Q - 1: cross_dev [m, N, p], mean_p_host [m, p], cov_pp_host [m, p, p],
+ * z_host [S, p + 1, m].  form: where the m thread-private Cholesky factors live - 0 LDS (bad arguments where the workgroup's share
+ * of the LDS does not hold them, nothing is launched), 1 a chunked global workspace, -1 the faster one by measurement (the
+ * workspace); both forms give the same bits.  NaN for a row of which ANY target's joint covariance does not factor at any jitter level. */
+int bbh_ehvi_pending(bbh_handle* h, int32_t log, int32_t m, const double* mean_dev, const double* var_dev, const double* cross_dev,
+                     int64_t N, int64_t p, const double* mean_p_host, const double* cov_pp_host, const double* cell_lo_host,
+                     const double* cell_up_host, int64_t C, const double* z_host, int64_t S, int32_t form, const uint8_t* alive_dev,
+                     double* scores_dev);
+int bbh_ehvi_last_form(bbh_handle* h); /* of the last bbh_ehvi_pending launch: 0 LDS, 1 workspace, -1 none yet */
+
 /* Box decomposition of the non-dominated region, one per MC sample (host code, no device work; BoTorch's
  * FastNondominatedPartitioning inside qLogNoisyExpectedHypervolumeImprovement, built at
  * baybe/acquisition/_builder.py:319-324).  obj_host [S, n, m] oriented baseline objective samples, ref_host [m].
