@@ -189,6 +189,10 @@ SIGNATURES = {
          c_double_p, C.c_int64, c_double_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p],
     ),
     "bbh_ehvi_last_form": (C.c_int, [C.c_void_p]),
+    "bbh_nipv_set_points": (C.c_int, [C.c_void_p, c_double_p, C.c_int64, c_double_p]),
+    "bbh_nipv_gain": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, c_double_p, c_double_p, C.c_void_p,
+                                C.c_void_p]),
+    "bbh_last_nipv_form": (C.c_int, [C.c_void_p]),
     "bbh_analytic_acq": (
         C.c_int,
         [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_int32,

@@ -10,8 +10,11 @@ from __future__ import annotations
 
 from typing import ClassVar
 
+import attrs
 from attrs import define, field
-from attrs.validators import ge, instance_of
+from attrs.converters import optional as optional_c
+from attrs.validators import ge, gt, instance_of, le
+from attrs.validators import optional as optional_v
 
 
 @define(frozen=True)
@@ -239,11 +242,77 @@ qNEI, qLogNEI = qNoisyExpectedImprovement, qLogNoisyExpectedImprovement
 _NOISY_EI = {c.abbreviation: c for c in (qNoisyExpectedImprovement, qLogNoisyExpectedImprovement)}
 
 
-def convert_acqf(acqf, ehvi: str = "refuse"):
+def _convert_sampling_method(value) -> str:
+    """``DiscreteSamplingMethod`` (utils/sampling_algorithms.py:175-182) by value or member, kept as its value."""
+    name = str(getattr(value, "value", value))
+    if name not in ("Random", "FPS"):
+        raise ValueError(f"'{value}' is not a valid DiscreteSamplingMethod")
+    return name
+
+
+@define(frozen=True)
+class qNegIntegratedPosteriorVariance:
+    """Monte Carlo based negative integrated posterior variance (``acqfs.py:29-138``): the reference's acquisition function for
+    active learning.  Scored by ``baybe_amd.nipv.HipNIPV`` under the recommender's ``nipv="device"``; no samples are drawn - the
+    value is a closed form of the posterior covariance with the integration points (``csrc/bbh_nipv.hip``)."""
+
+    abbreviation: ClassVar[str] = "qNIPV"
+    kind: ClassVar[str] = "qNIPV"
+    supports_batching: ClassVar[bool] = True
+    supports_pending_experiments: ClassVar[bool] = True
+    supports_multi_output: ClassVar[bool] = False
+    is_mc: ClassVar[bool] = True
+    is_analytic: ClassVar[bool] = False
+
+    sampling_n_points: int | None = field(validator=optional_v([instance_of(int), gt(0)]), default=None)
+    """Number of data points sampled for integrating the posterior.  Cannot be used if ``sampling_fraction`` is not None."""
+
+    sampling_fraction: float | None = field(converter=optional_c(float), validator=optional_v([gt(0.0), le(1.0)]))
+    """Fraction of data sampled for integrating the posterior.  Cannot be used if ``sampling_n_points`` is not None."""
+
+    sampling_method: str = field(converter=_convert_sampling_method, default="Random")
+    """Sampling strategy used for integrating the posterior ("Random" or "FPS")."""
+
+    @sampling_fraction.default
+    def _default_sampling_fraction(self):
+        """If no sampling quantities are provided, use all points by default."""
+        return 1.0 if self.sampling_n_points is None else None
+
+    @sampling_fraction.validator
+    def _validate_sampling_fraction(self, attr, value) -> None:
+        """If both sampling quantities are specified, raise an error."""
+        if None not in (self.sampling_fraction, self.sampling_n_points):
+            raise ValueError(
+                f"For '{self.__class__.__name__}', the attributes '{attr.name}' and "
+                f"'{attrs.fields(self.__class__).sampling_n_points.name}' cannot "
+                f"be specified at the same time."
+            )
+
+
+qNIPV = qNegIntegratedPosteriorVariance
+
+
+def convert_acqf(acqf, ehvi: str = "refuse", nipv: str = "refuse"):
     """``baybe.acquisition.utils.convert_acqf``: accept abbreviations / BayBE objects.  ``ehvi``: the recommender's setting of that
     name - "device" converts qEHVI / qLogEHVI (abbreviations, full names, our instances, the reference's objects by class name),
-    "refuse" refuses them and names the setting."""
+    "refuse" refuses them and names the setting.  ``nipv``: the same for qNIPV (``baybe_amd.nipv``)."""
     name = acqf if isinstance(acqf, str) else type(acqf).__name__
+    if name in ("qNIPV", "qNegIntegratedPosteriorVariance"):
+        if nipv != "device":
+            from baybe_amd.exceptions import IncompatibleAcquisitionFunctionError
+
+            raise IncompatibleAcquisitionFunctionError(
+                f"The HIP recommender scores the MC / analytic EI-PI-UCB-SR families, qNEI / qLogNEI, qLogNEHVI / qNEHVI and "
+                f"qLogNParEGO on the device; '{name}' is not available on this path. Pass nipv='device' to the recommender to "
+                f"score qNIPV on the device over discrete search spaces."
+            )
+        if isinstance(acqf, qNegIntegratedPosteriorVariance):
+            return acqf
+        if isinstance(acqf, str):
+            return qNegIntegratedPosteriorVariance()
+        return qNegIntegratedPosteriorVariance(sampling_n_points=getattr(acqf, "sampling_n_points", None),
+                                               sampling_fraction=getattr(acqf, "sampling_fraction", None),
+                                               sampling_method=getattr(acqf, "sampling_method", "Random"))
     for abbr, cls in _EHVI.items():
         if name in (abbr, cls.__name__):
             if ehvi != "device":

@@ -47,6 +47,8 @@ static bbh_switches bbh_read_switches() {
       {"BBH_NEHVI_SLICES", INT, 0, nullptr, &S::nehvi_slices},
       {"BBH_NEHVI_PK", NOT, '0', &S::nehvi_pk, nullptr},
       {"BBH_EHVI_SLICE", INT, 0, nullptr, &S::ehvi_slice},
+      {"BBH_NIPV_TILE", INT, 0, nullptr, &S::nipv_tile},
+      {"BBH_NIPV_SLICE", INT, 0, nullptr, &S::nipv_slice},
       {"BBH_NEI_FUSED", NOT, '0', &S::nei_fused, nullptr},
       {"BBH_SELECT", NOT, '0', &S::select_on, nullptr},
       {"BBH_SELECT_MAPPED", NOT, '0', &S::select_mapped, nullptr},
@@ -145,6 +147,7 @@ extern "C" int bbh_destroy(bbh_handle* h) {
   bbh_fps_destroy(h);
   bbh_flow_destroy(h);
   bbh_postgrad_destroy(h);
+  bbh_nipv_destroy(h);
   bbh_free_model_public(h);
   if (h->d_ws) hipFree(h->d_ws);
   if (h->fit_stream) {
@@ -323,6 +326,7 @@ extern "C" int bbh_trim(bbh_handle* h, int64_t keep_bytes) {
     h->d_kvcache = nullptr;
     h->kvcache_bytes = 0;
   }
+  if (bbh_nipv_resident_bytes(h) > (size_t)keep_bytes) bbh_nipv_destroy(h);
   if (h->have_model && sizeof(double) * (size_t)h->np * (size_t)h->np * 6 > (size_t)keep_bytes) bbh_free_model_public(h);
   return 0;
 }

@@ -217,6 +217,8 @@ struct bbh_switches {
   int nehvi_slices = INT_MIN;     // BBH_NEHVI_SLICES: sample slices of the linear-domain qLogNEHVI kernel (unset: by size)
   bool nehvi_pk = true;           // BBH_NEHVI_PK=0: double-precision fat-minimum factors in the linear-domain qLogNEHVI kernel (A/B)
   int ehvi_slice = INT_MIN;       // BBH_EHVI_SLICE: MC samples per slice of the qEHVI / qLogEHVI kernels, 0 = all in one slice (unset: 16; A/B)
+  int nipv_tile = 16;             // BBH_NIPV_TILE=32: two 16-candidate row tiles per workgroup of the qNIPV gain kernel instead of one (A/B: measured slower, KERNELS.md 4.15; falls back to one where 32 rows do not fit the LDS)
+  int nipv_slice = 512;           // BBH_NIPV_SLICE: integration-point columns per slice of the qNIPV gain kernel, 0 = all in one slice (A/B)
   bool nei_fused = true;          // BBH_NEI_FUSED=0: qNEI / qLogNEI through bbh_posterior_columns_sm + bbh_nei_q1 instead of the fused scoring pass (A/B, verification)
   bool select_on = true;          // BBH_SELECT=0: top-k / argmax by k rounds of workgroup argmax (A/B)
   bool select_mapped = true;      // BBH_SELECT_MAPPED=0: selection results through a device buffer + copy instead of host-mapped stores (A/B)
@@ -405,6 +407,7 @@ struct bbh_handle {
   void* select_state = nullptr;   // chunk keys, result block and base-sample tables of the selection kernels (bbh_select.hip)
   void* sobol_state = nullptr;    // staging of the device-side base-sample draw (bbh_sobol.hip), null until bbh_sobol_normal_dev
   void* fps_state = nullptr;      // keys, minimum distances and result blocks of farthest point sampling (bbh_fps.hip)
+  void* nipv_state = nullptr;     // resident [A ; H] operand and integration points of qNIPV (bbh_nipv.hip), null until bbh_nipv_set_points
   void* postgrad_state = nullptr; // (K + s2 I)^-1 and column constants of the current factorisation (bbh_postgrad.hip), null until bbh_posterior_grad
   // timing
   int timing = 0;  // 0 off, 1 every kernel family, otherwise 2 x (bit mask of the families that record events)
@@ -512,6 +515,9 @@ void bbh_fps_reset(bbh_handle* h);       // bbh_fps.hip: ends the selection in p
 void bbh_flow_destroy(bbh_handle* h);    // bbh_fitflow.hip
 void bbh_postgrad_destroy(bbh_handle* h);     // bbh_postgrad.hip
 void bbh_postgrad_invalidate(bbh_handle* h);  // bbh_postgrad.hip: a new factorisation - the cached (K + s2 I)^-1 is stale
+void bbh_nipv_destroy(bbh_handle* h);         // bbh_nipv.hip
+void bbh_nipv_invalidate(bbh_handle* h);      // bbh_nipv.hip: a new factorisation - the resident A = (K + s2 I)^-1 K(X, P) is stale
+size_t bbh_nipv_resident_bytes(const bbh_handle* h);  // bbh_nipv.hip: what the resident operand pins
 bool bbh_fit_flow_launch(bbh_handle* h, const double* theta_dev, double* out_dev, int* info_dev, bool tail_only, const double* theta_host = nullptr,
                          bool split = false, int skip_mt = 0, bool prepare_only = false);  // split: two launches - the factorisation with K^-1's tiles, then everything behind them; skip_mt: tail form without the M-tile roles
 bool bbh_fit_flow_mt_args(bbh_handle* h, void* pd_mt_args_out);  // arguments for K^-1's tiles inside the factorisation launch, matching the next tail launch  // 64 < np <= 1024: the whole evaluation as one dataflow launch, or (tail_only) everything after the factorisation; false: not eligible

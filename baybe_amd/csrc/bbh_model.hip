@@ -1008,6 +1008,7 @@ extern "C" int bbh_factorize(bbh_handle* h, const double* theta_host, double* ji
   if (rc) return rc;
   h->factorized = false;
   bbh_postgrad_invalidate(h);
+  bbh_nipv_invalidate(h);
   if (bbh_is_rff(h)) {
     rc = bbh_rff_factorize(h);
     if (rc) return rc;

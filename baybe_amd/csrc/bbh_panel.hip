@@ -928,6 +928,12 @@ static int bbh_unfused_chunk(bbh_handle* h, const double* X_dev, int64_t Nc, int
   return 0;
 }
 
+// the same for other translation units (bbh_nipv.hip): Kst = K(X*, X) [Ncpad, np] and V = Kst L^-T of one row chunk
+int bbh_kstar_solve_chunk(bbh_handle* h, const double* X_dev, int64_t Nc, int64_t ldx, double* Kst, double* V, const double* d_lo,
+                          const double* d_hi) {
+  return bbh_unfused_chunk(h, X_dev, Nc, ldx, Kst, V, d_lo, d_hi);
+}
+
 // models the fused kernels are not instantiated for: composite kernels, the piecewise-polynomial family
 bool bbh_materialised_only(const bbh_handle* h) { return h->F > 1 || h->desc.kernel_kind > BBH_KERNEL_RBF; }
 

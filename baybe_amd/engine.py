@@ -912,6 +912,45 @@ class HipGP:
         """Storage of the factors in the last joint ``ehvi_acq`` launch: 0 LDS, 1 workspace, -1 none yet."""
         return int(self._lib.bbh_ehvi_last_form(self._h))
 
+    def nipv_set_points(self, P: np.ndarray) -> np.ndarray:
+        """Integration points of qNIPV, ``P`` [M, d] rows of the candidates' representation: builds A = (K + s2 I)^-1 K(X, P) from the
+        current factorisation and keeps it resident until the next ``factorize``.  Returns var(p_j) [M] (original target scale)."""
+        P = np.ascontiguousarray(np.atleast_2d(P), dtype=np.float64)
+        if P.shape[1] < self.spec.d:
+            raise ValueError("integration points must be [M, d]")
+        P = np.ascontiguousarray(P[:, : self.spec.d])
+        var_p = np.empty(P.shape[0])
+        self._check(self._lib.bbh_nipv_set_points(self._h, _dp(P), P.shape[0], _dp(var_p)), "bbh_nipv_set_points")
+        self._nipv_M = P.shape[0]
+        return var_p
+
+    def nipv_gain(self, X, var, cross=None, H=None, ginv=None, alive=None):
+        """gain [N] of qNIPV (``include/baybe_hip.h``): the integrated variance that adding x to the handle's b pending points removes,
+        summed over the integration points.  ``var`` [N] from ``posterior``; with pending points ``cross`` [N, b] from ``cross_cov``,
+        ``H`` [b, M] = G^-1 cov(B, P) and ``ginv`` [b, b] = G^-1, G = cov(B, B) + s2 I.  -inf where ``alive`` is 0."""
+        torch = self._torch()
+        X = self._as_dev(X)
+        N = X.shape[0]
+        b = getattr(self, "_p", 0)
+        if var.shape != (N,) or not var.is_contiguous():
+            raise ValueError("var must be a contiguous [N] tensor")
+        hp = gp = cp = None
+        if b:
+            if cross is None or H is None or ginv is None:
+                raise ValueError("with pending points pass cross [N, b], H [b, M] and ginv [b, b]")
+            H, ginv = np.ascontiguousarray(H, dtype=np.float64), np.ascontiguousarray(ginv, dtype=np.float64)
+            if tuple(cross.shape) != (N, b) or not cross.is_contiguous() or H.shape != (b, getattr(self, "_nipv_M", -1)) or ginv.shape != (b, b):
+                raise ValueError("with pending points pass cross [N, b], H [b, M] and ginv [b, b]")
+            hp, gp, cp = _dp(H), _dp(ginv), cross.data_ptr()
+        gain = torch.empty(N, dtype=torch.float64, device=X.device)
+        self._check(self._lib.bbh_nipv_gain(self._h, X.data_ptr(), N, X.stride(0), var.data_ptr(), cp, hp, gp,
+                                            alive.data_ptr() if alive is not None else None, gain.data_ptr()), "bbh_nipv_gain")
+        return gain
+
+    def nipv_last_form(self) -> int:
+        """Row tiles per workgroup of the last ``nipv_gain`` launch: 0 one (16 candidates), 1 two (32), -1 none yet."""
+        return int(self._lib.bbh_last_nipv_form(self._h))
+
     def analytic_acq(self, kind: str, mean, var, best_f: float = 0.0, sign: float = 1.0, beta: float = 0.2,
                      maximize: bool = True, alive=None):
         """Analytic acquisition values (PM, PSTD, UCB, EI, LogEI, PI) of N single candidates."""

@@ -501,6 +501,27 @@ int bbh_ehvi_pending(bbh_handle* h, int32_t log, int32_t m, const double* mean_d
                      double* scores_dev);
 int bbh_ehvi_last_form(bbh_handle* h); /* of the last bbh_ehvi_pending launch: 0 LDS, 1 workspace, -1 none yet */
 
+/* ---- qNegIntegratedPosteriorVariance (baybe/acquisition/acqfs.py: qNIPV) -------------------------------------------------------
+ * The variance that conditioning the GP on a t-batch [x ; B] removes at M integration points, B = the handle's b pending points
+ * (bbh_pending_set).  One Matern-1/2, Matern-3/2, Matern-5/2 or RBF kernel, one task, n <= 512.  With cov the posterior covariance
+ * given the training data, s2 the noise and every quantity in the target's original scale (as bbh_posterior's variance):
+ *   A = (K + s2 I)^-1 K(X, P) [n, M],   G = cov(B, B) + s2 I,   H = G^-1 cov(B, P) [b, M],
+ *   C_j(x) = k(x, p_j) - k(x, X) A[:, j] - cov(x, B) H[:, j],
+ *   gain(x) = sum_j C_j(x)^2 / (max(var(x) - cov(x, B) G^-1 cov(B, x), 0) + s2);
+ * qNIPV([x ; B]) = gain(x) / M - mean_j (var(p_j) - cov(p_j, B) H[:, j]).  The selection runs on gain (the constant would only
+ * throw away its low bits).
+ * bbh_nipv_set_points: once per recommendation, after bbh_factorize: P_host [M, d] rows of the candidates' representation; builds A
+ * from the factorisation (two multiplications by L^-1) and keeps it resident, padded to 64 columns; var_p_host [M] (may be null)
+ * receives var(p_j).  A new bbh_factorize invalidates it.  An M whose resident operand (np + 16) Mpad 8 bytes exceeds 256 MiB is
+ * refused with a text (M = 16384 at n = 512 takes 66 MiB).
+ * bbh_nipv_gain: var_dev [N] (bbh_posterior), cross_dev [N, b] (bbh_cross_cov), H_host [b, M], ginv_host [b, b] = G^-1; with b = 0
+ * the three may be null.  gain_dev [N]; -inf for a row with alive_dev[i] == 0.  The columns are cut into slices over a second grid
+ * dimension and the slices are added in slice order: two runs, and equal rows at different positions, give the same bits. */
+int bbh_nipv_set_points(bbh_handle* h, const double* P_host, int64_t M, double* var_p_host);
+int bbh_nipv_gain(bbh_handle* h, const double* X_dev, int64_t N, int64_t ldx, const double* var_dev, const double* cross_dev,
+                  const double* H_host, const double* ginv_host, const uint8_t* alive_dev, double* gain_dev);
+int bbh_last_nipv_form(bbh_handle* h); /* of the last bbh_nipv_gain launch: 0 one 16-row tile per workgroup, 1 two; -1 none yet */
+
 /* Box decomposition of the non-dominated region, one per MC sample (host code, no device work; BoTorch's
  * FastNondominatedPartitioning inside qLogNoisyExpectedHypervolumeImprovement, built at
  * baybe/acquisition/_builder.py:319-324).  obj_host [S, n, m] oriented baseline objective samples, ref_host [m].
