@@ -19,11 +19,9 @@
 #include <type_traits>
 
 #include "bbh_common.h"
-#include "bbh_acqmath.h"  // TAU_RELU, bbh_fatplus_core, bbh_safe_sd
+#include "bbh_acqmath.h"  // TAU_RELU, TAU_MAX, bbh_fatplus_core, bbh_safe_sd
+#include "bbh_slices.h"   // sample slices of bbh_qlogei_pending_q_kernel: bounds, finish
 
-#define TAU_MAX 1e-2
-#define LOG_TAU_RELU -13.815510557964274  // log(1e-6)
-typedef float bbh_f2 __attribute__((ext_vector_type(2)));
 #ifndef BBH_PENDING_PK
 #define BBH_PENDING_PK 1  // (with BBH_PENDING_FAST) the u_r^2 terms of the fat maximum in packed single precision, two points at a time
 #endif
@@ -62,7 +60,7 @@ __global__ __launch_bounds__(256) void bbh_qlogei_q1_kernel(const double* __rest
   }
   for (; s < S; s++) s0 += bbh_fatplus_core<1>(fma(b, s_z[s], a));
   const double sum = (s0 + s1) + (s2 + s3);
-  scores[i] = log(TAU_RELU) + log(sum) - log((double)S);
+  scores[i] = LOG_TAU_RELU + log(sum) - log((double)S);
 }
 
 #include "bbh_joint.h"  // shared core of the joint q'-batch kernels: QMAX, tri, bbh_joint_factor, bbh_joint_draw, bbh_upload_joint
@@ -83,7 +81,7 @@ __device__ __forceinline__ double bbh_qlogei_joint_lse(const double* L, ST strid
     for (int r = 0; r < q; r++) {
       const double y = bbh_joint_draw(L, stride, r, (r == 0) ? m0 : mean_p[r - 1], zs);
       const double tt = (sign * y - best_f) * inv_tau;
-      const double v = log(TAU_RELU) + log(bbh_fatplus_core(tt));
+      const double v = LOG_TAU_RELU + log(bbh_fatplus_core(tt));
       li[r * li_stride] = v;
       mx = fmax(mx, v);
     }
@@ -185,39 +183,6 @@ __global__ __launch_bounds__(64) void bbh_qlogei_pending_kernel(
   scores[i] = bbh_qlogei_joint_lse(L, 64, p + 1, mean[i], s_mp, z, S, best_f, sign, li, 1);
 }
 
-// log(x) for positive, finite, normal x (the fat-softplus values and sums of squares below): exponent and
-// mantissa by v_frexp, m in [sqrt(1/2), sqrt(2)), log m = 2 atanh(s), s = (m - 1)/(m + 1) through a
-// v_rcp_f64 seed with two Newton steps, odd series to s^19 (|s| <= 0.1716: truncation 2e-17), two-word ln 2.
-// ~26 VALU instead of ~40 for the library call; relative error <= 3e-16 (also next to x = 1, where the
-// result is 2 s (1 + R) with no cancellation).
-__device__ __forceinline__ double bbh_fast_recip(double d) {
-  double y = __builtin_amdgcn_rcp(d);
-  y = fma(fma(-d, y, 1.0), y, y);
-  return fma(fma(-d, y, 1.0), y, y);
-}
-__device__ __forceinline__ double bbh_fast_log_pos(double x) {
-  double m = __builtin_amdgcn_frexp_mant(x);  // [0.5, 1)
-  int e = __builtin_amdgcn_frexp_exp(x);
-  const bool lowm = m < 0.70710678118654752440;
-  m = lowm ? 2.0 * m : m;
-  e = lowm ? e - 1 : e;
-  const double f = m - 1.0;
-  const double s = f * bbh_fast_recip(2.0 + f);
-  const double z = s * s;
-  double r = fma(z, 1.0 / 19.0, 1.0 / 17.0);
-  r = fma(r, z, 1.0 / 15.0);
-  r = fma(r, z, 1.0 / 13.0);
-  r = fma(r, z, 1.0 / 11.0);
-  r = fma(r, z, 1.0 / 9.0);
-  r = fma(r, z, 1.0 / 7.0);
-  r = fma(r, z, 1.0 / 5.0);
-  r = fma(r, z, 1.0 / 3.0);
-  const double lm = fma(2.0 * s * z, r, 2.0 * s);
-  const double ed = (double)e;
-  const double r2 = fma(ed, 6.93147180369123816490e-01, fma(ed, 1.90821492927058770002e-10, lm));
-  return (x < INFINITY) ? r2 : x;  // log(inf) = inf (NaN propagates)
-}
-
 // Register-resident form of bbh_qlogei_pending_kernel for q' = Q <= 14 (208 VGPRs at Q = 8, 2 waves per SIMD from Q = 9,
 // 1 from Q = 10; no spills up to Q = 13, Q = 14 reports 4 spilled VGPRs and no scratch memory: .vgpr_spill_count 4,
 // .private_segment_fixed_size 0; Q = 15, 16 spill further and run no faster than the LDS form): the packed Cholesky
@@ -230,7 +195,7 @@ __device__ __forceinline__ double bbh_fast_log_pos(double x) {
 // BBH_PENDING_LDS=1 and the 60 KB hand-over at Q = 14), the LDS form within 3e-11 of the oracle and this one within 2.1e-9
 // (tolerance 1e-8; profiles/joint_batch_observed_deviations.json).
 // SAMPLE SLICES (gridDim.y > 1, linear-domain form only): blockIdx.y takes the samples [y per, (y + 1) per) and writes the partial sum
-// of its terms to partial[y][i]; bbh_pending_finish_kernel adds the slices in a fixed order and takes the logarithm.  With one
+// of its terms to partial[y][i]; bbh_slices_finish_kernel (bbh_slices.h) adds the slices in a fixed order and takes the logarithm.  With one
 // thread per candidate a 1e5-row candidate set is 1563 wavefronts, 1.5 per SIMD, each one long dependent chain: the slices bring
 // the launch to the occupancy a 1e6-row set has (the joint Cholesky factor is recomputed per slice: Q^3 / 3 flops against
 // per x Q x 40).
@@ -241,10 +206,10 @@ __global__ __launch_bounds__(256) void bbh_qlogei_pending_q_kernel(
     double best_f, double sign, const uint8_t* __restrict__ alive, double* __restrict__ scores, double* __restrict__ partial) {
   extern __shared__ double s_zq[];  // [S * Q] base samples of this slice, then mean_p [Q - 1], cov_pp [(Q - 1)^2]
   constexpr int P = Q - 1;
-  const int per = (S_total + (int)gridDim.y - 1) / (int)gridDim.y;
-  const int s_begin = (int)blockIdx.y * per;
-  const int S = (s_begin + per <= S_total) ? per : (S_total > s_begin ? S_total - s_begin : 0);  // samples of this slice
-  z += (int64_t)s_begin * Q;
+  const int per = bbh_slice_per(S_total);
+  const bbh_slice sl = bbh_slice_bounds(S_total, per, (int)blockIdx.y);
+  const int S = sl.count;  // samples of this slice
+  z += (int64_t)sl.begin * Q;
   if (partial) scores = partial + (int64_t)blockIdx.y * N;
   double* s_mp = s_zq + (int64_t)per * Q;
   double* s_cpp = s_mp + P;
@@ -387,25 +352,16 @@ __global__ __launch_bounds__(256) void bbh_qlogei_pending_q_kernel(
   scores[i] = partial ? sum : LOG_TAU_RELU + log(sum) - log((double)S_total);
 }
 
-__global__ __launch_bounds__(256) void bbh_pending_finish_kernel(const double* __restrict__ partial, int slices, int64_t N, int S,
-                                                                 const uint8_t* __restrict__ alive, double* __restrict__ scores) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= N) return;
-  double total = 0.0;
-  for (int k = 0; k < slices; k++) total += partial[(int64_t)k * N + i];  // NaN (no positive definite factor) propagates
-  scores[i] = (alive && !alive[i]) ? -INFINITY : LOG_TAU_RELU + log(total) - log((double)S);
-}
-
 template <int Q>
-static void bbh_launch_pending_q(hipStream_t st, const double* mean, const double* var, const double* cross, int64_t N,
+static void bbh_launch_pending_q(bbh_handle* h, const double* mean, const double* var, const double* cross, int64_t N,
                                  const double* mp, const double* cpp, const double* z, int S, double best_f, double sign,
-                                 const uint8_t* alive, double* scores, int slices, double* partial) {
-  const int per = (S + slices - 1) / slices;
+                                 const uint8_t* alive, double* scores, int slices) {
+  double* partial = slices > 1 ? h->d_ws : nullptr;
+  const int per = bbh_slices_by_count(S, slices).per;
   const size_t lds = sizeof(double) * ((size_t)per * Q + (Q - 1) + (size_t)(Q - 1) * (Q - 1));
-  hipLaunchKernelGGL((bbh_qlogei_pending_q_kernel<Q>), dim3((unsigned)((N + 255) / 256), (unsigned)slices), dim3(256), lds, st, mean, var,
-                     cross, N, mp, cpp, z, S, best_f, sign, alive, scores, slices > 1 ? partial : nullptr);
-  if (slices > 1)
-    hipLaunchKernelGGL(bbh_pending_finish_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, partial, slices, N, S, alive, scores);
+  hipLaunchKernelGGL((bbh_qlogei_pending_q_kernel<Q>), dim3((unsigned)((N + 255) / 256), (unsigned)slices), dim3(256), lds, h->stream, mean,
+                     var, cross, N, mp, cpp, z, S, best_f, sign, alive, scores, partial);
+  if (slices > 1) bbh_slices_finish<BBH_FINISH_LOG_TAU_MEAN>(h, partial, slices, 1, N, S, alive, scores);  // NaN (no positive definite factor) propagates
 }
 
 // ---- first-index argmax -----------------------------------------------------------------------
@@ -628,8 +584,8 @@ static int bbh_qlogei_pending_impl(bbh_handle* h, const double* mean_dev, const 
 #endif
   bbh_timed_scope timed(h, BBH_TIMED_PENDING);
   if (!(reg_form && bbh_dispatch_q(p + 1, [&](auto Q) {
-          bbh_launch_pending_q<decltype(Q)::value>(h->stream, mean_dev, var_dev, cross_dev, N, d.mean_p, d.cov_pp, d.z, (int)S, best_f,
-                                                   sign, alive_dev, scores_dev, slices, h->d_ws);
+          bbh_launch_pending_q<decltype(Q)::value>(h, mean_dev, var_dev, cross_dev, N, d.mean_p, d.cov_pp, d.z, (int)S, best_f, sign,
+                                                   alive_dev, scores_dev, slices);
         })))
     hipLaunchKernelGGL(bbh_qlogei_pending_kernel, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, h->stream, mean_dev, var_dev,
                        cross_dev, N, p, d.mean_p, d.cov_pp, d.z, (int)S, best_f, sign, alive_dev, scores_dev);
@@ -889,486 +845,6 @@ extern "C" int bbh_score_qlogei(bbh_handle* h, const double* X_dev, int64_t N, i
   h->fuse_qz = nullptr;
   h->fuse_scores = nullptr;
   return rc;
-}
-
-// =================================================================================================
-// qLogNEHVI (q' = 1): per MC sample, log-sum over the cells of that sample's box decomposition of
-//   sum_o fatmin( log_fatplus(f_o - lo_o; tau_relu), loglen_o; tau_max ),  then logmeanexp over samples.
-// One thread per candidate; the cell data is uniform across the wave (scalar / broadcast loads).
-// =================================================================================================
-struct NehviArgs {
-  const double* tmat[BBH_MAX_OBJECTIVES];
-  const double* var[BBH_MAX_OBJECTIVES];
-  double sign[BBH_MAX_OBJECTIVES];
-  int m;
-  int64_t N;
-  int S;
-  const double* zx;        // [S, m]
-  const int64_t* cell_off; // [S + 1]
-  const double* cell_lo;   // [ncells, m]
-  const double* cell_ll;   // [ncells, m]
-  int sample_major;        // tmat[o] is [S, N] (bbh_posterior_columns_sm) instead of [N, S]
-  const uint8_t* alive;
-  double* scores;
-};
-
-__device__ __forceinline__ double bbh_fatmin2(double a, double b) {
-  // min(a,b) - tau log(1 + (alpha / (alpha + |a-b|/tau))^alpha), alpha = 2, tau = 1e-2
-  const double mn = fmin(a, b);
-  double diff = fabs(a - b);
-  if (!(diff == diff)) diff = INFINITY;  // (-inf) - (-inf)
-  // u = 2 / (2 + diff / tau) and log1p(u^2) through the short reciprocal / logarithm sequences (u^2 in (0, 1]:
-  // forming 1 + u^2 costs at most 1e-16 absolute, times tau = 1e-2); diff = inf gives u = 0 exactly
-  const double u = (diff < INFINITY) ? (2.0 * TAU_MAX) * bbh_fast_recip(fma(2.0, TAU_MAX, diff)) : 0.0;
-  return fma(-TAU_MAX, bbh_fast_log_pos(fma(u, u, 1.0)), mn);
-}
-
-template <int M>
-__global__ __launch_bounds__(256) void bbh_qlognehvi_kernel(const NehviArgs a) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= a.N) return;
-  if (a.alive && !a.alive[i]) {
-    a.scores[i] = -INFINITY;
-    return;
-  }
-  double sd[M], sg[M];
-  const double* trow[M];
-#pragma unroll
-  for (int o = 0; o < M; o++) {
-    sd[o] = bbh_safe_sd(a.var[o][i]);
-    sg[o] = a.sign[o];
-    trow[o] = a.sample_major ? a.tmat[o] + i : a.tmat[o] + i * (int64_t)a.S;
-  }
-  const int64_t tstride = a.sample_major ? a.N : 1;
-  const double inv_tau = 1.0 / TAU_RELU;
-  const double log_tau = log(TAU_RELU);
-  double sref = -INFINITY, ssum = 0.0;  // streaming log-sum-exp over MC samples
-  for (int s = 0; s < a.S; s++) {
-    double f[M];
-#pragma unroll
-    for (int o = 0; o < M; o++) f[o] = sg[o] * fma(sd[o], a.zx[(int64_t)s * M + o], trow[o][s * tstride]);
-    double cref = -INFINITY, csum = 0.0;  // streaming log-sum-exp over the cells of this sample
-    const int64_t c0 = a.cell_off[s], c1 = a.cell_off[s + 1];
-    for (int64_t c = c0; c < c1; c++) {
-      double la = 0.0;
-#pragma unroll
-      for (int o = 0; o < M; o++) {
-        const double t = (f[o] - a.cell_lo[c * M + o]) * inv_tau;
-        const double li = log_tau + bbh_fast_log_pos(bbh_fatplus_core(t));
-        la += bbh_fatmin2(li, a.cell_ll[c * M + o]);
-      }
-      if (la > cref) {
-        csum = csum * exp(cref - la) + 1.0;
-        cref = la;
-      } else if (la > -INFINITY) {
-        csum += exp(la - cref);
-      }
-    }
-    const double v = (cref > -INFINITY) ? cref + log(csum) : -INFINITY;
-    if (v > sref) {
-      ssum = ssum * exp(sref - v) + 1.0;
-      sref = v;
-    } else if (v > -INFINITY) {
-      ssum += exp(v - sref);
-    }
-  }
-  a.scores[i] = (sref > -INFINITY) ? sref + log(ssum) - log((double)a.S) : -INFINITY;
-}
-
-// The same value with the sums over cells and samples taken in the LINEAR domain:
-//   score = log( (1/S) sum_s sum_c prod_o exp(fatmin(li_o, ll_o)) ),
-//   exp(fatmin(a, b)) = min(e^a, e^b) (1 + u^2)^(-tau_max),  u = 2 tau_max / (2 tau_max + |a - b|),
-// where e^a = tau_relu fatplus(t) is at hand BEFORE any logarithm is taken and e^b is the cell's side length.  Every term is a
-// product of m side lengths >= ~1e-25 (the fat tail 0.1 tau_relu / (1 + t^2) at |t| <= 1e10), far inside the fp64 range, so
-// nothing needs the log domain; what the log-domain form pays per (cell, target) - two double-precision logarithms, and per
-// cell an exponential for the streaming log-sum-exp - shrinks to series and single-precision logarithms (see the loop body: the
-// power tau_max = 0.01 absorbs their error).  BBH_NEHVI_LOG=1 selects the log-domain kernel (A/B, tests).
-// One thread per candidate and SAMPLE SLICE (blockIdx.y of gridDim.y slices): with one thread per candidate a 1e5-row
-// candidate set is 1563 wavefronts - 1.5 per SIMD, each a long dependent chain - and the kernel ran at a fifth of the VALU
-// issue rate; the slices bring the launch to >= 8 waves per SIMD.  All lanes of a wave work on the same samples, so the
-// cell data stays wave-uniform (scalar loads).  The slices' partial sums are combined in a fixed order by
-// bbh_qlognehvi_finish_kernel (sums of positive terms in the linear domain: no atomics, reproducible).
-// delta = 1 - (1 + u^2)^(-tau_max) <= 0.007 of TWO (cell, target) terms at once, in packed single precision (v_pk_fma_f32 /
-// v_pk_mul_f32): the term is min(A, B) (1 - delta), so a relative error of ~1e-6 in delta is 7e-9 in the term - the same budget
-// the double-precision form below spends on its single-precision logarithms.  rho = min / max, x1 = 1 - rho (taken in double
-// precision, where it is exact next to rho = 1).  rho = 0 (cell unbounded above, or a ratio below the single-precision range):
-// log2 -> -inf, |li - ll| = inf, u = 0, delta = 0.
-__device__ __forceinline__ bbh_f2 bbh_fatmin_delta2(bbh_f2 rho, bbh_f2 x1) {
-  bbh_f2 ds = x1 * (1.0f / 7.0f) + (1.0f / 6.0f);
-  ds = ds * x1 + 0.2f;
-  ds = ds * x1 + 0.25f;
-  ds = ds * x1 + (1.0f / 3.0f);
-  ds = ds * x1 + 0.5f;
-  ds = ds * x1 + 1.0f;
-  ds = ds * x1;  // -log1p(-x1), x1 < 0.15
-  bbh_f2 dl;
-  dl.x = -0.6931471805599453f * __log2f(rho.x);
-  dl.y = -0.6931471805599453f * __log2f(rho.y);
-  bbh_f2 den;
-  den.x = (x1.x < 0.15f ? ds.x : dl.x) + (float)(2.0 * TAU_MAX);
-  den.y = (x1.y < 0.15f ? ds.y : dl.y) + (float)(2.0 * TAU_MAX);
-  bbh_f2 u;
-  u.x = __builtin_amdgcn_rcpf(den.x);
-  u.y = __builtin_amdgcn_rcpf(den.y);
-  u = u * (float)(2.0 * TAU_MAX);
-  const bbh_f2 w = u * u;
-  bbh_f2 lps = w * -0.25f + (1.0f / 3.0f);
-  lps = lps * w - 0.5f;
-  lps = lps * w + 1.0f;
-  lps = lps * w;  // log1p(w), w < 0.03
-  bbh_f2 lp;
-  lp.x = (w.x < 0.03f) ? lps.x : 0.6931471805599453f * __log2f(1.0f + w.x);
-  lp.y = (w.y < 0.03f) ? lps.y : 0.6931471805599453f * __log2f(1.0f + w.y);
-  const bbh_f2 x = lp * (float)TAU_MAX;  // in [0, 0.00694]
-  bbh_f2 d = x * (-1.0f / 24.0f) + (1.0f / 6.0f);
-  d = d * x - 0.5f;
-  d = d * x + 1.0f;
-  return d * x;  // 1 - exp(-x)
-}
-
-// PK: the (1 + u^2)^(-tau_max) factors in packed single precision, two cells at a time (default); PK = false is the double-precision
-// sequence (BBH_NEHVI_PK=0: A/B, tests)
-template <int M, bool PK>
-__global__ __launch_bounds__(256) void bbh_qlognehvi_lin_kernel(const NehviArgs a, const double* __restrict__ cell_len,
-                                                                double* __restrict__ partial) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= a.N) return;
-  const int per = (a.S + (int)gridDim.y - 1) / (int)gridDim.y;
-  const int s_begin = (int)blockIdx.y * per, s_end = (s_begin + per < a.S) ? s_begin + per : a.S;
-  if (a.alive && !a.alive[i]) {
-    partial[(int64_t)blockIdx.y * a.N + i] = 0.0;
-    return;
-  }
-  double sd[M], sg[M];
-  const double* trow[M];
-  const int64_t tstride = a.sample_major ? a.N : 1;  // between consecutive samples of this candidate
-#pragma unroll
-  for (int o = 0; o < M; o++) {
-    sd[o] = bbh_safe_sd(a.var[o][i]);
-    sg[o] = a.sign[o];
-    trow[o] = a.sample_major ? a.tmat[o] + i : a.tmat[o] + i * (int64_t)a.S;
-  }
-  const double inv_tau = 1.0 / TAU_RELU;
-  double total = 0.0;
-  for (int s = s_begin; s < s_end; s++) {
-    double f[M];
-#pragma unroll
-    for (int o = 0; o < M; o++) f[o] = sg[o] * fma(sd[o], a.zx[(int64_t)s * M + o], trow[o][s * tstride]);
-    const int64_t c0 = a.cell_off[s], c1 = a.cell_off[s + 1];
-    double ssum = 0.0;
-    int64_t c = c0;
-    if (PK) {
-      for (; c < c1; c += 2) {
-        const int64_t cb = (c + 1 < c1) ? c + 1 : c;  // odd cell count: the last cell is paired with itself, its twin is not added
-        double pa = 1.0, pb = 1.0;
-#pragma unroll
-        for (int o = 0; o < M; o++) {
-          double mn2[2];
-          bbh_f2 rho, x1, rc;
-#pragma unroll
-          for (int h = 0; h < 2; h++) {
-            const int64_t cc = h ? cb : c;
-            const double B = cell_len[cc * M + o];
-            const double A = TAU_RELU * bbh_fatplus_core<1>((f[o] - a.cell_lo[cc * M + o]) * inv_tau);
-            const double mn = fmin(A, B), mxv = fmax(A, B);
-            // rho = min / max and x1 = 1 - rho = (max - min) / max, each with its own relative accuracy (x1 next to rho = 1, where the
-            // term is sensitive; rho next to 0, where delta ~ 1e-8 would vanish in 1 - x1): the difference in double precision,
-            // the quotients in single precision - no double-precision reciprocal
-            const float gap = (float)(mxv - mn), mnf = (float)mn, mxf = (float)mxv;
-            mn2[h] = mn;
-            if (h) {
-              x1.y = gap;
-              rho.y = mnf;
-              rc.y = __builtin_amdgcn_rcpf(mxf);
-            } else {
-              x1.x = gap;
-              rho.x = mnf;
-              rc.x = __builtin_amdgcn_rcpf(mxf);
-            }
-          }
-          x1 = x1 * rc;  // max = inf (cell unbounded above): inf * 0 = NaN -> 1;  rho = min * 0 = 0
-          rho = rho * rc;
-          x1.x = (x1.x == x1.x) ? x1.x : 1.0f;
-          x1.y = (x1.y == x1.y) ? x1.y : 1.0f;
-          const bbh_f2 dl = bbh_fatmin_delta2(rho, x1);
-          pa *= fma(-mn2[0], (double)dl.x, mn2[0]);
-          pb *= fma(-mn2[1], (double)dl.y, mn2[1]);
-        }
-        ssum += pa;
-        if (c + 1 < c1) ssum += pb;
-      }
-    }
-    for (; !PK && c < c1; c++) {
-      double prod = 1.0;
-#pragma unroll
-      for (int o = 0; o < M; o++) {
-        const double B = cell_len[c * M + o];
-        const double fp = bbh_fatplus_core((f[o] - a.cell_lo[c * M + o]) * inv_tau);
-        const double A = TAU_RELU * fp;
-        // |li - ll| = -log(rho), rho = min(A, B) / max(A, B): a 7-term series of -log1p(-x) next to rho = 1 (x = 1 - rho <
-        // 0.15, where the term is sensitive: d log(term) = u^3 d|li - ll|), single precision beyond (u < 0.11 there: an error of
-        // 1e-7 moves the term by 1e-10 relative).  B = inf (cell unbounded above): rho = 0, u = 0.  No double-precision
-        // logarithm is left: inside a wave some lane is nearly always close to rho = 1, so a wave-uniform skip never skipped.
-        const double mn = fmin(A, B), mxv = fmax(A, B);
-        double inv = __builtin_amdgcn_rcp(mxv);
-        inv = fma(fma(-mxv, inv, 1.0), inv, inv);
-        const double rho = (mxv < INFINITY) ? mn * inv : 0.0;
-        const double x1 = 1.0 - rho;
-        double ds = fma(x1, 1.0 / 7.0, 1.0 / 6.0);
-        ds = fma(ds, x1, 0.2);
-        ds = fma(ds, x1, 0.25);
-        ds = fma(ds, x1, 1.0 / 3.0);
-        ds = fma(ds, x1, 0.5);
-        ds = fma(ds, x1, 1.0);
-        ds *= x1;
-        const double dl = -0.6931471805599453 * (double)__log2f((float)rho);  // rho = 0 -> inf
-        const double diff = (x1 < 0.15) ? ds : dl;
-        const double u = (2.0 * TAU_MAX) * __builtin_amdgcn_rcp(fma(2.0, TAU_MAX, diff));  // bare seed (2^-26); diff = inf -> 0
-        const double w = u * u;
-        // log1p(w), w in [0, 1]: series below 0.03 (error w^5 / 5 < 5e-9), single precision above (1.2e-7) - times tau_max = 0.01
-        const double lps = w * fma(w, fma(w, fma(w, -0.25, 1.0 / 3.0), -0.5), 1.0);
-        const double lpf = 0.6931471805599453 * (double)__log2f((float)(1.0 + w));
-        const double lp = (w < 0.03) ? lps : lpf;
-        const double x = TAU_MAX * lp;  // in [0, 0.00694]
-        const double e = fma(x, fma(x, fma(x, fma(x, fma(x, -1.0 / 120.0, 1.0 / 24.0), -1.0 / 6.0), 0.5), -1.0), 1.0);  // exp(-x)
-        prod *= mn * e;
-      }
-      ssum += prod;
-    }
-    total += ssum;
-  }
-  partial[(int64_t)blockIdx.y * a.N + i] = total;
-}
-
-__global__ __launch_bounds__(256) void bbh_qlognehvi_finish_kernel(const double* __restrict__ partial, int slices, int64_t N, int S,
-                                                                   const uint8_t* __restrict__ alive, double* __restrict__ scores) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= N) return;
-  double total = 0.0;
-  for (int k = 0; k < slices; k++) total += partial[(int64_t)k * N + i];
-  scores[i] = (total > 0.0 && !(alive && !alive[i])) ? log(total) - log((double)S) : -INFINITY;
-}
-
-static int bbh_qlognehvi_impl(bbh_handle* h, int32_t m, int64_t N, const double* const* tmat_dev,
-                             const double* const* var_dev, const double* sign_host, const double* zx_host, int64_t S,
-                             const int64_t* cell_off_host, const double* cell_lo_host, const double* cell_loglen_host,
-                             const uint8_t* alive_dev, double* scores_dev, bool sample_major);
-
-extern "C" int bbh_qlognehvi(bbh_handle* h, int32_t m, int64_t N, const double* const* tmat_dev,
-                             const double* const* var_dev, const double* sign_host, const double* zx_host, int64_t S,
-                             const int64_t* cell_off_host, const double* cell_lo_host, const double* cell_loglen_host,
-                             const uint8_t* alive_dev, double* scores_dev) {
-  return bbh_qlognehvi_impl(h, m, N, tmat_dev, var_dev, sign_host, zx_host, S, cell_off_host, cell_lo_host, cell_loglen_host, alive_dev,
-                            scores_dev, false);
-}
-
-extern "C" int bbh_qlognehvi_sm(bbh_handle* h, int32_t m, int64_t N, const double* const* tmat_dev,
-                                const double* const* var_dev, const double* sign_host, const double* zx_host, int64_t S,
-                                const int64_t* cell_off_host, const double* cell_lo_host, const double* cell_loglen_host,
-                                const uint8_t* alive_dev, double* scores_dev) {
-  return bbh_qlognehvi_impl(h, m, N, tmat_dev, var_dev, sign_host, zx_host, S, cell_off_host, cell_lo_host, cell_loglen_host, alive_dev,
-                            scores_dev, true);
-}
-
-// launches with every operand on the device: a.zx, a.cell_off, a.cell_lo, a.cell_ll set by the caller, len_dev = side lengths
-static int bbh_qlognehvi_run(bbh_handle* h, NehviArgs& a, const double* len_dev) {
-  const int m = a.m;
-  const int64_t N = a.N, S = a.S;
-  dim3 grid((unsigned)((N + 255) / 256)), block(256);
-  bbh_timed_scope timed(h, BBH_TIMED_NEHVI);
-  if (!h->sw.nehvi_log) {  // linear-domain sums (default)
-    const double* len = len_dev;
-    // sample slices: ~16 waves per SIMD (4 SIMDs per CU; 11.3 / 10.4 / 10.0 / 9.8 ms for 6 / 12 / 24 / 48 slices at 1e5 candidates), each slice at least 8 samples
-    const int64_t srows = h->slice_rows > 0 ? h->slice_rows : N;
-    int64_t slices = ((int64_t)16 * 4 * h->num_cu * 64 + srows - 1) / srows;
-    if (h->sw.nehvi_slices != INT_MIN) slices = h->sw.nehvi_slices;
-    if (slices > S / 8) slices = S / 8;
-    if (slices > 64) slices = 64;
-    if (slices < 1) slices = 1;
-    int rc = bbh_ensure_ws(h, sizeof(double) * (size_t)slices * (size_t)N);
-    if (rc) return rc;
-    dim3 sgrid(grid.x, (unsigned)slices);
-    if (!h->sw.nehvi_pk) {
-      switch (m) {
-        case 1: hipLaunchKernelGGL((bbh_qlognehvi_lin_kernel<1, false>), sgrid, block, 0, h->stream, a, len, h->d_ws); break;
-        case 2: hipLaunchKernelGGL((bbh_qlognehvi_lin_kernel<2, false>), sgrid, block, 0, h->stream, a, len, h->d_ws); break;
-        case 3: hipLaunchKernelGGL((bbh_qlognehvi_lin_kernel<3, false>), sgrid, block, 0, h->stream, a, len, h->d_ws); break;
-        default: hipLaunchKernelGGL((bbh_qlognehvi_lin_kernel<4, false>), sgrid, block, 0, h->stream, a, len, h->d_ws); break;
-      }
-    } else {
-      switch (m) {
-        case 1: hipLaunchKernelGGL((bbh_qlognehvi_lin_kernel<1, true>), sgrid, block, 0, h->stream, a, len, h->d_ws); break;
-        case 2: hipLaunchKernelGGL((bbh_qlognehvi_lin_kernel<2, true>), sgrid, block, 0, h->stream, a, len, h->d_ws); break;
-        case 3: hipLaunchKernelGGL((bbh_qlognehvi_lin_kernel<3, true>), sgrid, block, 0, h->stream, a, len, h->d_ws); break;
-        default: hipLaunchKernelGGL((bbh_qlognehvi_lin_kernel<4, true>), sgrid, block, 0, h->stream, a, len, h->d_ws); break;
-      }
-    }
-    hipLaunchKernelGGL(bbh_qlognehvi_finish_kernel, grid, block, 0, h->stream, h->d_ws, (int)slices, N, (int)S, a.alive, a.scores);
-    BBH_HIP_TRY(h, hipGetLastError());
-    return 0;
-  }
-  switch (m) {
-    case 1: hipLaunchKernelGGL(bbh_qlognehvi_kernel<1>, grid, block, 0, h->stream, a); break;
-    case 2: hipLaunchKernelGGL(bbh_qlognehvi_kernel<2>, grid, block, 0, h->stream, a); break;
-    case 3: hipLaunchKernelGGL(bbh_qlognehvi_kernel<3>, grid, block, 0, h->stream, a); break;
-    default: hipLaunchKernelGGL(bbh_qlognehvi_kernel<4>, grid, block, 0, h->stream, a); break;
-  }
-  BBH_HIP_TRY(h, hipGetLastError());
-  return 0;
-}
-
-static void bbh_nehvi_fill_args(NehviArgs& a, int32_t m, int64_t N, const double* const* tmat_dev, const double* const* var_dev,
-                                const double* sign_host, int64_t S, const uint8_t* alive_dev, double* scores_dev, bool sample_major) {
-  for (int o = 0; o < BBH_MAX_OBJECTIVES; o++) {
-    a.tmat[o] = o < m ? tmat_dev[o] : nullptr;
-    a.var[o] = o < m ? var_dev[o] : nullptr;
-    a.sign[o] = o < m ? sign_host[o] : 1.0;
-  }
-  a.m = m;
-  a.N = N;
-  a.S = (int)S;
-  a.alive = alive_dev;
-  a.scores = scores_dev;
-  a.sample_major = sample_major ? 1 : 0;
-}
-
-static int bbh_qlognehvi_impl(bbh_handle* h, int32_t m, int64_t N, const double* const* tmat_dev,
-                             const double* const* var_dev, const double* sign_host, const double* zx_host, int64_t S,
-                             const int64_t* cell_off_host, const double* cell_lo_host, const double* cell_loglen_host,
-                             const uint8_t* alive_dev, double* scores_dev, bool sample_major) {
-  if (!h) return -1;
-  if (m < 1 || m > BBH_MAX_OBJECTIVES || N < 0 || S < 1 || !tmat_dev || !var_dev || !sign_host || !zx_host ||
-      !cell_off_host || !scores_dev) {
-    h->err = "bbh_qlognehvi: bad arguments (1 <= m <= 4)";
-    return -1;
-  }
-  if (N == 0) return 0;
-  BBH_HIP_TRY(h, hipSetDevice(h->device));
-  const int64_t ncells = cell_off_host[S];
-  if (ncells < 0 || (ncells > 0 && (!cell_lo_host || !cell_loglen_host))) {
-    h->err = "bbh_qlognehvi: inconsistent cell arrays";
-    return -1;
-  }
-  // one upload: zx [S*m] | cell_lo [ncells*m] | cell_ll [ncells*m] | cell_len [ncells*m] | cell_off [S+1] (int64, 8-byte slots)
-  const size_t nd = (size_t)S * m + 3 * (size_t)ncells * m;
-  std::vector<double> buf(nd + (size_t)S + 1);
-  memcpy(buf.data(), zx_host, sizeof(double) * S * m);
-  if (ncells > 0) {
-    memcpy(buf.data() + S * m, cell_lo_host, sizeof(double) * ncells * m);
-    memcpy(buf.data() + S * m + ncells * m, cell_loglen_host, sizeof(double) * ncells * m);
-    double* len = buf.data() + S * m + 2 * ncells * m;  // side lengths e^ll (inf for cells unbounded above)
-    for (int64_t e = 0; e < ncells * m; e++) len[e] = exp(cell_loglen_host[e]);
-  }
-  memcpy(buf.data() + nd, cell_off_host, sizeof(int64_t) * (S + 1));
-  int rc = bbh_upload_z(h, buf.data(), buf.size());
-  if (rc) return rc;
-  NehviArgs a;
-  bbh_nehvi_fill_args(a, m, N, tmat_dev, var_dev, sign_host, S, alive_dev, scores_dev, sample_major);
-  a.zx = h->d_z;
-  a.cell_lo = h->d_z + S * m;
-  a.cell_ll = h->d_z + S * m + ncells * m;
-  a.cell_off = (const int64_t*)(h->d_z + nd);
-  return bbh_qlognehvi_run(h, a, h->d_z + S * m + 2 * ncells * m);
-}
-
-// bbh_qlognehvi_sm against the device-resident cell lists of bbh_cells_build_dev on this handle: only the candidate's base
-// samples zx_host [S, m] travel.
-extern "C" int bbh_qlognehvi_cells(bbh_handle* h, int32_t m, int64_t N, const double* const* tmat_dev,
-                                   const double* const* var_dev, const double* sign_host, const double* zx_host, int64_t S,
-                                   const uint8_t* alive_dev, double* scores_dev) {
-  if (!h) return -1;
-  const bbh_nehvi_state* st = (const bbh_nehvi_state*)h->nehvi_state;
-  if (m < 1 || m > BBH_MAX_OBJECTIVES || N < 0 || S < 1 || !tmat_dev || !var_dev || !sign_host || !zx_host || !scores_dev || !st ||
-      st->S != S || st->m != m) {
-    h->err = "bbh_qlognehvi_cells: bad arguments, or no cell lists for this S and m on the handle (bbh_cells_build_dev)";
-    return -1;
-  }
-  if (N == 0) return 0;
-  BBH_HIP_TRY(h, hipSetDevice(h->device));
-  int rc = bbh_upload_z(h, zx_host, (size_t)S * m);
-  if (rc) return rc;
-  NehviArgs a;
-  bbh_nehvi_fill_args(a, m, N, tmat_dev, var_dev, sign_host, S, alive_dev, scores_dev, true);
-  a.zx = h->d_z;
-  a.cell_off = st->off();
-  a.cell_lo = st->lo();
-  a.cell_ll = st->ll();
-  return bbh_qlognehvi_run(h, a, st->len());
-}
-
-// ---- Pareto frequency of the baseline points over MC samples (pruning) ---------------------------
-template <int M>
-__global__ __launch_bounds__(256) void bbh_pareto_freq_kernel(const double* __restrict__ obj, int n, const double* __restrict__ ref,
-                                                              unsigned long long* __restrict__ counts) {
-  extern __shared__ double s_obj[];  // [n, M] of this sample
-  const double* src = obj + (int64_t)blockIdx.x * n * M;
-  for (int e = threadIdx.x; e < n * M; e += blockDim.x) s_obj[e] = src[e];
-  __syncthreads();
-  for (int i = threadIdx.x; i < n; i += blockDim.x) {
-    double yi[M];
-    bool above = true;
-#pragma unroll
-    for (int o = 0; o < M; o++) {
-      yi[o] = s_obj[i * M + o];
-      above = above && (yi[o] > ref[o]);
-    }
-    bool dominated = false;
-    for (int j = 0; j < n && !dominated; j++) {
-      bool ge = true, gt = false;
-#pragma unroll
-      for (int o = 0; o < M; o++) {
-        const double yj = s_obj[j * M + o];
-        ge = ge && (yj >= yi[o]);
-        gt = gt || (yj > yi[o]);
-      }
-      dominated = ge && gt;
-    }
-    if (above && !dominated) atomicAdd(&counts[i], 1ULL);
-  }
-}
-
-static int bbh_pareto_frequency_impl(bbh_handle* h, const double* obj, bool on_device, int64_t S, int64_t n, int32_t m,
-                                     const double* ref_host, int64_t* counts_host) {
-  if (!h) return -1;
-  if (!obj || !ref_host || !counts_host || S < 1 || n < 1 || n > 8192 / (m > 0 ? m : 1) || m < 1 ||
-      m > BBH_MAX_OBJECTIVES) {
-    h->err = "bbh_pareto_frequency: bad arguments (n * m <= 8192, 1 <= m <= 4)";
-    return -1;
-  }
-  BBH_HIP_TRY(h, hipSetDevice(h->device));
-  const size_t nobj = on_device ? 0 : (size_t)S * n * m;
-  int rc = bbh_ensure_ws(h, sizeof(double) * (nobj + m + n));
-  if (rc) return rc;
-  double* d_obj = h->d_ws;
-  double* d_ref = d_obj + nobj;
-  unsigned long long* d_cnt = (unsigned long long*)(d_ref + m);
-  if (!on_device) BBH_HIP_TRY(h, hipMemcpyAsync(d_obj, obj, sizeof(double) * nobj, hipMemcpyHostToDevice, h->stream));
-  const double* src = on_device ? obj : d_obj;
-  BBH_HIP_TRY(h, hipMemcpyAsync(d_ref, ref_host, sizeof(double) * m, hipMemcpyHostToDevice, h->stream));
-  BBH_HIP_TRY(h, hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long) * n, h->stream));
-  const size_t lds = sizeof(double) * n * m;
-  dim3 grid((unsigned)S), block(256);
-  switch (m) {
-    case 1: hipLaunchKernelGGL(bbh_pareto_freq_kernel<1>, grid, block, lds, h->stream, src, (int)n, d_ref, d_cnt); break;
-    case 2: hipLaunchKernelGGL(bbh_pareto_freq_kernel<2>, grid, block, lds, h->stream, src, (int)n, d_ref, d_cnt); break;
-    case 3: hipLaunchKernelGGL(bbh_pareto_freq_kernel<3>, grid, block, lds, h->stream, src, (int)n, d_ref, d_cnt); break;
-    default: hipLaunchKernelGGL(bbh_pareto_freq_kernel<4>, grid, block, lds, h->stream, src, (int)n, d_ref, d_cnt); break;
-  }
-  BBH_HIP_TRY(h, hipGetLastError());
-  BBH_HIP_TRY(h, hipMemcpyAsync(counts_host, d_cnt, sizeof(int64_t) * n, hipMemcpyDeviceToHost, h->stream));
-  BBH_HIP_TRY(h, hipStreamSynchronize(h->stream));
-  return 0;
-}
-
-extern "C" int bbh_pareto_frequency(bbh_handle* h, const double* obj_host, int64_t S, int64_t n, int32_t m,
-                                    const double* ref_host, int64_t* counts_host) {
-  return bbh_pareto_frequency_impl(h, obj_host, false, S, n, m, ref_host, counts_host);
-}
-
-// ... with the objective samples already on the device (bbh_nehvi_samples wrote them): nothing but the counts travels
-extern "C" int bbh_pareto_frequency_dev(bbh_handle* h, const double* obj_dev, int64_t S, int64_t n, int32_t m,
-                                        const double* ref_host, int64_t* counts_host) {
-  return bbh_pareto_frequency_impl(h, obj_dev, true, S, n, m, ref_host, counts_host);
 }
 
 // =================================================================================================

@@ -18,9 +18,7 @@
 #include "bbh_acqmath.h"
 #include "bbh_joint.h"
 
-#define AG_TAU_MAX 1e-2
 #define AG_PIVOT_RTOL 1e-8
-#define AG_LOG_TAU_RELU -13.815510557964274  // log(1e-6)
 
 __global__ __launch_bounds__(64) void bbh_qlogei_partials_kernel(const double* __restrict__ mean, const double* __restrict__ var,
                                                                  const double* __restrict__ cross, int64_t N, int p,
@@ -95,17 +93,17 @@ __global__ __launch_bounds__(64) void bbh_qlogei_partials_kernel(const double* _
     double acc = 0.0, acc3 = 0.0;
 #pragma unroll 1
     for (int r = 0; r < q; r++) {
-      const double u = 2.0 / (2.0 + (mx - li[r * 64]) / AG_TAU_MAX);
+      const double u = 2.0 / (2.0 + (mx - li[r * 64]) / TAU_MAX);
       acc = fma(u, u, acc);
       acc3 = fma(u * u, u, acc3);
     }
-    const double fm = mx + AG_TAU_MAX * log(acc);
+    const double fm = mx + TAU_MAX * log(acc);
     const double e = exp(fm);
     sum += e;
     if (good) {
 #pragma unroll 1
       for (int r = 0; r < q; r++) {
-        const double u = 2.0 / (2.0 + (mx - li[r * 64]) / AG_TAU_MAX);
+        const double u = 2.0 / (2.0 + (mx - li[r * 64]) / TAU_MAX);
         double dli = u * u * u / acc;
         if (r == kstar) dli += 1.0 - acc3 / acc;
         const double yb = e * dli * dl[r * 64];
@@ -149,7 +147,7 @@ __global__ __launch_bounds__(256) void bbh_qlogei_partials_finish_kernel(const d
   if (i >= N) return;
   double total = 0.0;
   for (int k = 0; k < slices; k++) total += psum[(int64_t)k * N + i];  // NaN (no positive definite factor) propagates
-  scores[i] = AG_LOG_TAU_RELU + log(total) - log((double)S);
+  scores[i] = LOG_TAU_RELU + log(total) - log((double)S);
   for (int j = 0; j < np1; j++) {
     double g = 0.0;
     for (int k = 0; k < slices; k++) g += ppart[((int64_t)k * N + i) * np1 + j];

@@ -449,8 +449,8 @@ inline int64_t bbh_round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; 
 #define BBH_LDS_DEFAULT_LIMIT ((size_t)48 * 1024)
 __attribute__((visibility("hidden"))) hipError_t bbh_allow_lds(int device, const void* kernel, size_t bytes);
 
-// Device-resident box decompositions of one qLogNEHVI selection step (bbh_nehvi.hip: bbh_cells_build_dev writes them,
-// bbh_qlognehvi_cells in bbh_acq.hip scores against them).
+// Device-resident box decompositions of one qLogNEHVI / qNEHVI selection step (bbh_nehvi.hip: bbh_cells_build_dev writes them,
+// bbh_qlognehvi_cells and bbh_qnehvi_cells in bbh_qnehvi.hip score against them).
 struct bbh_nehvi_state {
   int64_t S = 0, total = 0, cap = 0;  // samples, cells in all samples, cell capacity per sample
   int m = 0;

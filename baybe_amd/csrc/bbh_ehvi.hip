@@ -34,13 +34,13 @@
 #include <vector>
 
 #include "bbh_common.h"
-#include "bbh_acqmath.h"  // TAU_RELU, bbh_fatplus_core, bbh_safe_sd
+#include "bbh_acqmath.h"  // TAU_RELU, TAU_MAX, bbh_fatplus_core, bbh_safe_sd
 #include "bbh_joint.h"    // tri, bbh_joint_factor, bbh_joint_draw
+#include "bbh_slices.h"   // slice bounds, finish kernel, dispatch
 
 namespace {
 
 constexpr int EH_SLICE = 16;                            // MC samples per slice (env BBH_EHVI_SLICE; 0: all samples in one slice)
-constexpr double EH_TAU_MAX = 1e-2;
 constexpr double EH_UPPER_CLAMP = 1e10;                 // cell_upper_bounds.clamp_max(1e10) in the log form
 constexpr size_t EH_LDS_BYTES = (size_t)80 << 10;       // form 0: at most this much LDS per workgroup
 constexpr size_t EH_WS_BYTES = (size_t)512 << 20;       // workspace bound of form 1 (env BBH_QBIG_WS_MB)
@@ -52,12 +52,12 @@ struct EhCells {
   int C;
 };
 
-__device__ __forceinline__ double eh_log_fatplus(double x) { return log(TAU_RELU) + log(bbh_fatplus_core<2>(x * (1.0 / TAU_RELU))); }
+__device__ __forceinline__ double eh_log_fatplus(double x) { return LOG_TAU_RELU + log(bbh_fatplus_core<2>(x * (1.0 / TAU_RELU))); }
 
 // fatmin over the pair (a, b), both finite: -fatmax(-a, -b) with tau_max and alpha = 2
 __device__ __forceinline__ double eh_fatmin2(double a, double b) {
-  const double u = 2.0 / (2.0 + fabs(a - b) / EH_TAU_MAX);
-  return fmin(a, b) - EH_TAU_MAX * log1p(u * u);
+  const double u = 2.0 / (2.0 + fabs(a - b) / TAU_MAX);
+  return fmin(a, b) - TAU_MAX * log1p(u * u);
 }
 
 // streaming logsumexp: (ref, sum) with value ref + log(sum), started at (-inf, 0); a NaN term makes the sum NaN
@@ -97,7 +97,7 @@ __global__ __launch_bounds__(256) void bbh_ehvi_q1_kernel(const double* __restri
   if (i >= N) return;
   if (alive && !alive[i]) return;  // (the finish kernel writes -inf without reading the partials)
   const int k = (int)blockIdx.y;
-  const int s0 = k * slice, s1 = (s0 + slice < S) ? s0 + slice : S;
+  const bbh_slice sl = bbh_slice_bounds(S, slice, k);
   double mu[M], sd[M];
 #pragma unroll
   for (int o = 0; o < M; o++) {
@@ -106,7 +106,7 @@ __global__ __launch_bounds__(256) void bbh_ehvi_q1_kernel(const double* __restri
   }
   double ref = -INFINITY, sum = 0.0;
 #pragma unroll 1
-  for (int s = s0; s < s1; s++) {
+  for (int s = sl.begin; s < sl.end; s++) {
     double y[M];
 #pragma unroll
     for (int o = 0; o < M; o++) y[o] = fma(sd[o], z[(int64_t)s * M + o], mu[o]);
@@ -155,7 +155,7 @@ __global__ __launch_bounds__(64) void bbh_ehvi_pending_kernel(int m, const doubl
   const int64_t i = row0 + local;
   if (alive && !alive[i]) return;
   const int k = (int)blockIdx.y;
-  const int s0 = k * slice, s1 = (s0 + slice < S) ? s0 + slice : S;
+  const bbh_slice sl = bbh_slice_bounds(S, slice, k);
   const int q = p + 1, triq = q * (q + 1) / 2, qm = q * m;
   double* L = WS ? Lws + (int64_t)k * chunk + local : s_dyn + tid;
   const ST stride = WS ? (ST)ws_stride : (ST)64;
@@ -175,7 +175,7 @@ __global__ __launch_bounds__(64) void bbh_ehvi_pending_kernel(int m, const doubl
   }
   double ref = -INFINITY, sum = 0.0;
 #pragma unroll 1
-  for (int s = s0; s < s1; s++) {
+  for (int s = sl.begin; s < sl.end; s++) {
     const double* zs = z + (int64_t)s * qm;
 #pragma unroll 1
     for (int j = 0; j < m; j++) {
@@ -215,10 +215,10 @@ __global__ __launch_bounds__(64) void bbh_ehvi_pending_kernel(int m, const doubl
               if (size > 1) {  // fat minimum of the members (one member: the value itself)
                 double w = 0.0;
                 for (int bits = A; bits; bits &= bits - 1) {
-                  const double u = 2.0 / (2.0 + (av[(__builtin_ctz(bits) * m + j) * 64] - mn) / EH_TAU_MAX);
+                  const double u = 2.0 / (2.0 + (av[(__builtin_ctz(bits) * m + j) * 64] - mn) / TAU_MAX);
                   w = fma(u, u, w);
                 }
-                mn -= EH_TAU_MAX * log(w);
+                mn -= TAU_MAX * log(w);
               }
               acc += eh_fatmin2(mn, ll[j]);
             } else {
@@ -254,35 +254,6 @@ __global__ __launch_bounds__(64) void bbh_ehvi_pending_kernel(int m, const doubl
       sum += csum;
   }
   eh_store_partial<LOG>(partial, ldn, i, k, LOG ? ref : sum, sum);
-}
-
-// the slices' partials in slice order -> score
-template <bool LOG>
-__global__ __launch_bounds__(256) void bbh_ehvi_finish_kernel(const double* __restrict__ partial, int slices, int64_t N, int S,
-                                                              const uint8_t* __restrict__ alive, double* __restrict__ scores) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= N) return;
-  if (alive && !alive[i]) {
-    scores[i] = -INFINITY;
-    return;
-  }
-  if (!LOG) {
-    double total = 0.0;
-    for (int k = 0; k < slices; k++) total += partial[(int64_t)(2 * k) * N + i];
-    scores[i] = total / (double)S;
-    return;
-  }
-  double ref = -INFINITY, sum = 0.0;
-  for (int k = 0; k < slices; k++) {
-    const double rk = partial[(int64_t)(2 * k) * N + i], sk = partial[(int64_t)(2 * k + 1) * N + i];
-    if (rk > ref) {
-      sum = sum * exp(ref - rk) + sk;
-      ref = rk;
-    } else {
-      sum += (sk == 0.0) ? 0.0 : sk * exp(rk - ref);
-    }
-  }
-  scores[i] = ref + log(sum) - log((double)S);
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------
@@ -331,10 +302,10 @@ size_t eh_lds_bytes(int m, int q, bool ws) {
   return sizeof(double) * 64 * ((ws ? 0 : (size_t)m * (q * (q + 1) / 2)) + 2 * (size_t)q * m + (size_t)m);
 }
 
+// the slices' partials (two rows per slice) in slice order -> score
 template <bool LOG>
 void eh_finish(bbh_handle* h, const double* partial, int slices, int64_t N, int64_t S, const uint8_t* alive_dev, double* scores_dev) {
-  hipLaunchKernelGGL(bbh_ehvi_finish_kernel<LOG>, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, h->stream, partial, slices, N, (int)S,
-                     alive_dev, scores_dev);
+  bbh_slices_finish<LOG ? BBH_FINISH_LSE_PAIRS : BBH_FINISH_MEAN>(h, partial, slices, 2, N, S, alive_dev, scores_dev);
 }
 
 template <int M, bool LOG>
@@ -377,22 +348,17 @@ extern "C" int bbh_ehvi_q1(bbh_handle* h, int32_t log, int32_t m, const double* 
   eh_put_cells(buf, nz, m, cell_lo_host, cell_up_host, C);
   int rc = bbh_upload_z(h, buf.data(), buf.size());
   if (rc) return rc;
-  const int slice = eh_slice_len(h, S), slices = (int)((S + slice - 1) / slice);
-  rc = bbh_ensure_ws(h, sizeof(double) * 2 * (size_t)slices * (size_t)N);
+  const bbh_slicing sl = bbh_slices_by_len(S, eh_slice_len(h, S));
+  rc = bbh_ensure_ws(h, sizeof(double) * 2 * (size_t)sl.count * (size_t)N);
   if (rc) return rc;
   const EhCells cells = {h->d_z + nz, h->d_z + nz + nc, h->d_z + nz + 2 * nc, (int)C};
   bbh_timed_scope timed(h, BBH_TIMED_Q1);
-#define EH_Q1(M)                                                                                                           \
-  if (log)                                                                                                                 \
-    eh_launch_q1<M, true>(h, mean_dev, var_dev, N, h->d_z, (int)S, slice, slices, cells, alive_dev, scores_dev);           \
-  else                                                                                                                     \
-    eh_launch_q1<M, false>(h, mean_dev, var_dev, N, h->d_z, (int)S, slice, slices, cells, alive_dev, scores_dev)
-  switch (m) {
-    case 2: EH_Q1(2); break;
-    case 3: EH_Q1(3); break;
-    default: EH_Q1(4); break;
-  }
-#undef EH_Q1
+  bbh_dispatch_m<2>(m, [&](auto M) {
+    bbh_dispatch_flag(log != 0, [&](auto LOG) {
+      eh_launch_q1<decltype(M)::value, decltype(LOG)::value>(h, mean_dev, var_dev, N, h->d_z, (int)S, sl.per, sl.count, cells, alive_dev,
+                                                             scores_dev);
+    });
+  });
   BBH_HIP_TRY(h, hipGetLastError());
   return 0;
 }
@@ -436,22 +402,22 @@ extern "C" int bbh_ehvi_pending(bbh_handle* h, int32_t log, int32_t m, const dou
   const double *d_z = h->d_z, *d_mp = d_z + nz, *d_cpp = d_mp + nmp, *d_cells = d_cpp + ncpp;
   const EhCells cells = {d_cells, d_cells + nc, d_cells + 2 * nc, (int)C};
   const int* d_tab = (const int*)(d_cells + 3 * nc);
-  const int slice = eh_slice_len(h, S), slices = (int)((S + slice - 1) / slice);
+  const bbh_slicing sl = bbh_slices_by_len(S, eh_slice_len(h, S));
+  const int slice = sl.per, slices = sl.count;
   const size_t lds = eh_lds_bytes(m, q, ws);
   const size_t npartial = 2 * (size_t)slices * (size_t)N;
   if (!ws) {
     rc = bbh_ensure_ws(h, sizeof(double) * npartial);
     if (rc) return rc;
     bbh_timed_scope timed(h, BBH_TIMED_PENDING);
-    if (log) {
-      BBH_HIP_TRY(h, (eh_launch_pending<false, true>(h, lds, N, slices, m, mean_dev, var_dev, cross_dev, N, 0, (int)p, d_mp, d_cpp, d_z, (int)S,
-                                                      slice, cells, d_tab, alive_dev, h->d_ws, nullptr, 0)));
-      eh_finish<true>(h, h->d_ws, slices, N, S, alive_dev, scores_dev);
-    } else {
-      BBH_HIP_TRY(h, (eh_launch_pending<false, false>(h, lds, N, slices, m, mean_dev, var_dev, cross_dev, N, 0, (int)p, d_mp, d_cpp, d_z, (int)S,
-                                                       slice, cells, d_tab, alive_dev, h->d_ws, nullptr, 0)));
-      eh_finish<false>(h, h->d_ws, slices, N, S, alive_dev, scores_dev);
-    }
+    const hipError_t launched = bbh_dispatch_flag(log != 0, [&](auto LOG) {
+      constexpr bool L = decltype(LOG)::value;
+      const hipError_t e = eh_launch_pending<false, L>(h, lds, N, slices, m, mean_dev, var_dev, cross_dev, N, 0, (int)p, d_mp, d_cpp, d_z, (int)S,
+                                                       slice, cells, d_tab, alive_dev, h->d_ws, nullptr, 0);
+      if (e == hipSuccess) eh_finish<L>(h, h->d_ws, slices, N, S, alive_dev, scores_dev);
+      return e;
+    });
+    BBH_HIP_TRY(h, launched);
     BBH_HIP_TRY(h, hipGetLastError());
     h->last_ehvi_form = 0;
     return 0;
@@ -467,19 +433,17 @@ extern "C" int bbh_ehvi_pending(bbh_handle* h, int32_t log, int32_t m, const dou
   if (rc) return rc;
   double* Lws = h->d_ws + npartial;
   bbh_timed_scope timed(h, BBH_TIMED_PENDING);
-  for (int64_t c0 = 0; c0 < N; c0 += chunk) {
-    const int64_t nrows = std::min(chunk, N - c0);
-    if (log)
-      BBH_HIP_TRY(h, (eh_launch_pending<true, true>(h, lds, nrows, slices, m, mean_dev, var_dev, cross_dev, N, c0, (int)p, d_mp, d_cpp, d_z,
-                                                     (int)S, slice, cells, d_tab, alive_dev, h->d_ws, Lws, chunk)));
-    else
-      BBH_HIP_TRY(h, (eh_launch_pending<true, false>(h, lds, nrows, slices, m, mean_dev, var_dev, cross_dev, N, c0, (int)p, d_mp, d_cpp, d_z,
-                                                      (int)S, slice, cells, d_tab, alive_dev, h->d_ws, Lws, chunk)));
-  }
-  if (log)
-    eh_finish<true>(h, h->d_ws, slices, N, S, alive_dev, scores_dev);
-  else
-    eh_finish<false>(h, h->d_ws, slices, N, S, alive_dev, scores_dev);
+  const hipError_t launched = bbh_dispatch_flag(log != 0, [&](auto LOG) {
+    constexpr bool L = decltype(LOG)::value;
+    for (int64_t c0 = 0; c0 < N; c0 += chunk) {
+      const hipError_t e = eh_launch_pending<true, L>(h, lds, std::min(chunk, N - c0), slices, m, mean_dev, var_dev, cross_dev, N, c0, (int)p, d_mp,
+                                                      d_cpp, d_z, (int)S, slice, cells, d_tab, alive_dev, h->d_ws, Lws, chunk);
+      if (e != hipSuccess) return e;
+    }
+    eh_finish<L>(h, h->d_ws, slices, N, S, alive_dev, scores_dev);
+    return hipSuccess;
+  });
+  BBH_HIP_TRY(h, launched);
   BBH_HIP_TRY(h, hipGetLastError());
   h->last_ehvi_form = 1;
   return 0;

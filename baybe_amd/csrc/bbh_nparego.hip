@@ -18,8 +18,9 @@
 // same samples, so z_x and best_s are scalar loads and the scalarisation constants kernel arguments.  A slice is a FIXED number of
 // samples (not a function of the candidate count): a candidate's partial sums, and with them its score, do not depend on which
 // chunk of a chunked pass it sits in.  The slices' sums of fatplus terms (linear domain, as bbh_nei_term<true>) are combined
-// in slice order by a finish kernel: no atomics, identical rows score bit-identically.
+// in slice order by the finish kernel of bbh_slices.h: no atomics, identical rows score bit-identically.
 #include "bbh_acqmath.h"
+#include "bbh_slices.h"
 
 namespace {
 
@@ -66,9 +67,7 @@ __global__ __launch_bounds__(256) void bbh_scalarized_best_kernel(const double* 
 }
 
 struct NparegoArgs {
-  const double* tmat[BBH_MAX_OBJECTIVES];  // [S, N] sample-major conditional means
-  const double* var[BBH_MAX_OBJECTIVES];   // [N]
-  double sign[BBH_MAX_OBJECTIVES];
+  bbh_targets t;  // tmat [S, N] sample-major
   NparegoScal sc;
   int64_t N;
   int S;
@@ -81,7 +80,7 @@ template <int M>
 __device__ __forceinline__ double np_term(const NparegoArgs& a, const double* sd, int64_t i, int s) {
   double f[M];
 #pragma unroll
-  for (int o = 0; o < M; o++) f[o] = a.sign[o] * fma(sd[o], a.zx[(int64_t)s * M + o], a.tmat[o][(int64_t)s * a.N + i]);
+  for (int o = 0; o < M; o++) f[o] = a.t.sign[o] * fma(sd[o], a.zx[(int64_t)s * M + o], a.t.tmat[o][(int64_t)s * a.N + i]);
   const double u = np_scalarize<M>(a.sc, f) - a.best[s];
   return bbh_fatplus_core<2>(u * (1.0 / TAU_RELU));
 }
@@ -91,34 +90,24 @@ template <int M>
 __global__ __launch_bounds__(256) void bbh_nparego_q1_kernel(const NparegoArgs a, double* __restrict__ partial) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= a.N) return;
-  const int s_begin = (int)blockIdx.y * NP_SLICE;
-  const int s_end = (s_begin + NP_SLICE < a.S) ? s_begin + NP_SLICE : a.S;
+  const bbh_slice sl = bbh_slice_bounds(a.S, NP_SLICE, (int)blockIdx.y);
   if (a.alive && !a.alive[i]) {
     partial[(int64_t)blockIdx.y * a.N + i] = 0.0;
     return;
   }
   double sd[M];
 #pragma unroll
-  for (int o = 0; o < M; o++) sd[o] = bbh_safe_sd(a.var[o][i]);
+  for (int o = 0; o < M; o++) sd[o] = bbh_safe_sd(a.t.var[o][i]);
   double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;  // independent chains: 4 M loads in flight per lane
-  int s = s_begin;
-  for (; s + 3 < s_end; s += 4) {
+  int s = sl.begin;
+  for (; s + 3 < sl.end; s += 4) {
     s0 += np_term<M>(a, sd, i, s);
     s1 += np_term<M>(a, sd, i, s + 1);
     s2 += np_term<M>(a, sd, i, s + 2);
     s3 += np_term<M>(a, sd, i, s + 3);
   }
-  for (; s < s_end; s++) s0 += np_term<M>(a, sd, i, s);
+  for (; s < sl.end; s++) s0 += np_term<M>(a, sd, i, s);
   partial[(int64_t)blockIdx.y * a.N + i] = (s0 + s1) + (s2 + s3);
-}
-
-__global__ __launch_bounds__(256) void bbh_nparego_finish_kernel(const double* __restrict__ partial, int slices, int64_t N, int S,
-                                                                 const uint8_t* __restrict__ alive, double* __restrict__ scores) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= N) return;
-  double total = 0.0;
-  for (int k = 0; k < slices; k++) total += partial[(int64_t)k * N + i];
-  scores[i] = (alive && !alive[i]) ? -INFINITY : bbh_nei_finish<true>(total, S);
 }
 
 bool np_fill_scal(NparegoScal& sc, int32_t m, const double* w, const double* hi, const double* inv) {
@@ -149,12 +138,9 @@ int np_scalarized_best(bbh_handle* h, const char* what, const double* Fb_dev, in
     BBH_HIP_TRY(h, hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long) * nb, h->stream));
   }
   const dim3 grid((unsigned)((S + 255) / 256)), block(256);
-  switch (m) {
-    case 1: hipLaunchKernelGGL(bbh_scalarized_best_kernel<1>, grid, block, 0, h->stream, Fb_dev, S, nb, sc, best_dev, d_cnt); break;
-    case 2: hipLaunchKernelGGL(bbh_scalarized_best_kernel<2>, grid, block, 0, h->stream, Fb_dev, S, nb, sc, best_dev, d_cnt); break;
-    case 3: hipLaunchKernelGGL(bbh_scalarized_best_kernel<3>, grid, block, 0, h->stream, Fb_dev, S, nb, sc, best_dev, d_cnt); break;
-    default: hipLaunchKernelGGL(bbh_scalarized_best_kernel<4>, grid, block, 0, h->stream, Fb_dev, S, nb, sc, best_dev, d_cnt); break;
-  }
+  bbh_dispatch_m(m, [&](auto M) {
+    hipLaunchKernelGGL(bbh_scalarized_best_kernel<decltype(M)::value>, grid, block, 0, h->stream, Fb_dev, S, nb, sc, best_dev, d_cnt);
+  });
   BBH_HIP_TRY(h, hipGetLastError());
   if (counts_host) {
     BBH_HIP_TRY(h, hipMemcpyAsync(counts_host, d_cnt, sizeof(int64_t) * nb, hipMemcpyDeviceToHost, h->stream));
@@ -194,18 +180,13 @@ extern "C" int bbh_nparego_q1(bbh_handle* h, int32_t m, int64_t N, const double*
     h->err = "bbh_nparego_q1: bad arguments (1 <= m <= 4, 1 <= S <= 8192, weights >= 0, finite 1 / (hi - lo) > 0)";
     return -1;
   }
-  for (int o = 0; o < BBH_MAX_OBJECTIVES; o++) {
-    a.tmat[o] = o < m ? tmat_sm_dev[o] : nullptr;
-    a.var[o] = o < m ? var_dev[o] : nullptr;
-    a.sign[o] = o < m ? sign_host[o] : 1.0;
-    if (o < m && N > 0 && (!a.tmat[o] || !a.var[o])) {
-      h->err = "bbh_nparego_q1: bad arguments (a target without conditional means or variances)";
-      return -1;
-    }
+  if (!bbh_fill_targets(a.t, m, N, tmat_sm_dev, var_dev, sign_host)) {
+    h->err = "bbh_nparego_q1: bad arguments (a target without conditional means or variances)";
+    return -1;
   }
   if (N == 0) return 0;
   BBH_HIP_TRY(h, hipSetDevice(h->device));
-  const int64_t slices = (S + NP_SLICE - 1) / NP_SLICE;
+  const int slices = bbh_slices_by_len(S, NP_SLICE).count;
   int rc = bbh_ensure_ws(h, sizeof(double) * (size_t)slices * (size_t)N);
   if (rc) return rc;
   a.N = N;
@@ -214,14 +195,9 @@ extern "C" int bbh_nparego_q1(bbh_handle* h, int32_t m, int64_t N, const double*
   a.best = best_dev;
   a.alive = alive_dev;
   bbh_timed_scope timed(h, BBH_TIMED_Q1);
-  const dim3 grid((unsigned)((N + 255) / 256)), sgrid(grid.x, (unsigned)slices), block(256);
-  switch (m) {
-    case 1: hipLaunchKernelGGL(bbh_nparego_q1_kernel<1>, sgrid, block, 0, h->stream, a, h->d_ws); break;
-    case 2: hipLaunchKernelGGL(bbh_nparego_q1_kernel<2>, sgrid, block, 0, h->stream, a, h->d_ws); break;
-    case 3: hipLaunchKernelGGL(bbh_nparego_q1_kernel<3>, sgrid, block, 0, h->stream, a, h->d_ws); break;
-    default: hipLaunchKernelGGL(bbh_nparego_q1_kernel<4>, sgrid, block, 0, h->stream, a, h->d_ws); break;
-  }
-  hipLaunchKernelGGL(bbh_nparego_finish_kernel, grid, block, 0, h->stream, h->d_ws, (int)slices, N, (int)S, alive_dev, scores_dev);
+  const dim3 sgrid((unsigned)((N + 255) / 256), (unsigned)slices), block(256);
+  bbh_dispatch_m(m, [&](auto M) { hipLaunchKernelGGL(bbh_nparego_q1_kernel<decltype(M)::value>, sgrid, block, 0, h->stream, a, h->d_ws); });
+  bbh_slices_finish<BBH_FINISH_LOG_TAU_MEAN>(h, h->d_ws, slices, 1, N, S, alive_dev, scores_dev);
   BBH_HIP_TRY(h, hipGetLastError());
   return 0;
 }

@@ -357,14 +357,15 @@ int bbh_analytic_acq(bbh_handle* h, int32_t kind, const double* mean_dev, const 
                      double best_f, double sign, double beta, int32_t maximize, const uint8_t* alive_dev,
                      double* scores_dev);
 
-/* ---- qLogNEHVI ---------------------------------------------------------------------- */
+/* ---- qLogNEHVI (bbh_qnehvi.hip, with the plain qNEHVI below) ------------------------- */
 #define BBH_MAX_OBJECTIVES 4
 /* q'=1 scores over m <= 4 independent outputs.  Per output o: tmat_dev[o] [N,S] conditional means
  * per MC sample (bbh_posterior_columns of the extended model), var_dev[o] [N] conditional variance;
  * sample f_o(x)_s = tmat[o][i][s] + sqrt(var[o][i]) zx_host[s*m+o], oriented by sign_host[o].
  * Cells of sample s: cell_off_host[s] .. cell_off_host[s+1] (prefix offsets, [S+1]); cell c stores
  * cell_lo_host[c*m+o] (lower bound) and cell_loglen_host[c*m+o] = log(min(upper,1e10) - lower).
- * score = logmeanexp_s logsumexp_c sum_o fatmin(log_fatplus(f_o - lo; 1e-6), loglen; 1e-2). */
+ * score = logmeanexp_s logsumexp_c sum_o fatmin(log_fatplus(f_o - lo; 1e-6), loglen; 1e-2).
+ * A null tmat_dev[o] or var_dev[o] of a used target with N > 0 is a bad-arguments error (-1), nothing is enqueued. */
 int bbh_qlognehvi(bbh_handle* h, int32_t m, int64_t N, const double* const* tmat_dev,
                   const double* const* var_dev, const double* sign_host, const double* zx_host, int64_t S,
                   const int64_t* cell_off_host, const double* cell_lo_host, const double* cell_loglen_host,

@@ -7,7 +7,7 @@ qEHVI) the kernel time is the handle's event timing of the launch (families "q1"
 kernel), with the factors in LDS and in the workspace, and - the A/B of KERNELS.md 4.14 - under two settings of BBH_EHVI_SLICE:
 unset (slices of 16 samples over a second grid dimension) and 0 (one thread per candidate walks all samples).
 
-Yardsticks, same rows, same process: the qLogNEHVI scoring pass (family "nehvi": the cell kernel of bbh_nehvi.hip after
+Yardsticks, same rows, same process: the qLogNEHVI scoring pass (family "nehvi": the cell kernel of bbh_qnehvi.hip after
 ``HipNEHVI.prepare``; its conditional-mean columns, family "columns", are reported next to it) and the m single-target posterior
 passes (family "posterior").  No ratio is a requirement.
 

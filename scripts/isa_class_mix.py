@@ -18,8 +18,8 @@ ROOT = Path(__file__).resolve().parents[1]
 CSRC = ROOT / "baybe_amd" / "csrc"
 TARGETS = {  # translation unit -> (substring of the mangled name, the name rocprofv3 prints)
     "bbh_acq.hip": [("bbh_qlogei_pending_q_kernelILi2", "bbh_qlogei_pending_q_kernel<2>"), ("bbh_qlogei_pending_q_kernelILi3", "bbh_qlogei_pending_q_kernel<3>"),
-                    ("bbh_qlogei_pending_q_kernelILi4", "bbh_qlogei_pending_q_kernel<4>"), ("bbh_qlogei_pending_q_kernelILi5", "bbh_qlogei_pending_q_kernel<5>"),
-                    ("bbh_qlognehvi_lin_kernelILi3ELb1", "bbh_qlognehvi_lin_kernel<3, true>")],
+                    ("bbh_qlogei_pending_q_kernelILi4", "bbh_qlogei_pending_q_kernel<4>"), ("bbh_qlogei_pending_q_kernelILi5", "bbh_qlogei_pending_q_kernel<5>")],
+    "bbh_qnehvi.hip": [("bbh_qlognehvi_lin_kernelILi3ELb1", "bbh_qlognehvi_lin_kernel<3, true>")],
     "bbh_select.hip": [("bbh_qlogei_q1s_kernel", "bbh_qlogei_q1s_kernel"), ("bbh_select_kernel", "bbh_select_kernel")],
     "bbh_fused_small_b.hip": [("bbh_small_posterior_kernelILi4ELi0ELi4", "bbh_small_posterior_kernel<4, 0, 4>")],
     "bbh_fused_small_a.hip": [("bbh_small_posterior_kernelILi2ELi0ELi2", "bbh_small_posterior_kernel<2, 0, 2>")],

@@ -311,3 +311,116 @@ def test_installed_columns_are_invalidated_not_freed_by_a_refit():
     assert np.array_equal(got, ref) and got.shape == want.shape == (N, S)
     g.close()
     fresh.close()
+
+
+# ---- the sample-slice scaffold (csrc/bbh_slices.h) at its edges -------------------------------------------------------------------
+EDGE_ROWS = np.r_[0:60, 250:257]  # of N = 257: the second 256-row block of the scoring grid holds one row
+EDGE_COMBOS = [(2, [1.0, -1.0]), (3, None)]
+
+
+def _edge_problem(m, signs):
+    """(X [257, d], Xt, signs, engines, models, ref point, rows of EDGE_ROWS coinciding with a baseline row) - shared with
+    tests/test_qnehvi_gpu.py through the cache of tests/_pareto_cases.py."""
+    from _pareto_cases import coincides_with_baseline, setup
+    from baybe_amd.nehvi import compute_ref_point
+
+    X, Xt, Y, signs, engines, models = setup(m, signs, N=257)
+    return X, Xt, signs, engines, models, compute_ref_point(Y * signs[None, :]), coincides_with_baseline(X[EDGE_ROWS], Xt)
+
+
+def _scorer_under(env, *args, **kwargs):
+    """A ``HipNEHVI`` whose handles are created under ``env`` (a handle reads its BBH_* switches when it is created)."""
+    import os
+
+    from baybe_amd.nehvi import HipNEHVI
+
+    keep = {k: os.environ.get(k) for k in env}
+    os.environ.update(env)
+    try:
+        return HipNEHVI(*args, **kwargs)
+    finally:
+        for k, val in keep.items():
+            os.environ.pop(k, None) if val is None else os.environ.__setitem__(k, val)
+
+
+@pytest.mark.parametrize("S", [1, 9, 33, 129])
+@pytest.mark.parametrize("m,signs", EDGE_COMBOS)
+def test_scores_match_oracle_at_the_slice_edges(m, signs, S):
+    """``bbh_qlognehvi_lin_kernel`` and the shared finish kernel where the slices are ragged, N = 257 (two blocks of candidates): S = 1
+    and S = 9 run one slice (S / 8 caps the count), S = 33 four slices of 9, 9, 9, 6 samples, S = 129 sixteen slices of 9 of which
+    the last but one has 3 samples and the last none.  Rows 0 ... 59 and 250 ... 256 against the oracle at ``NEHVI_ATOL`` (rows
+    coinciding with a baseline row excluded, as in ``test_scores_match_oracle``); one compared row is masked and scores -inf."""
+    import torch
+
+    from baybe_amd.nehvi import HipNEHVI
+    from conftest import record_deviation
+    from oracle import nehvi_oracle as no
+
+    X, Xt, signs, engines, models, ref, dup = _edge_problem(m, signs)
+    seed = 11
+    masked = int(EDGE_ROWS[~dup][3])
+    hv = HipNEHVI(engines, signs, Xt, ref, n_mc_samples=S, prune_baseline=False)
+    hv.prepare(seed)
+    alive = torch.ones(len(X), dtype=torch.uint8, device="cuda")
+    alive[masked] = 0
+    sg = hv.score(torch.from_numpy(X).cuda(), alive).cpu().numpy()
+    assert np.isneginf(sg[masked]) and np.isfinite(np.delete(sg, masked)).all()
+    so = no.NEHVIOracle(models, signs, Xt, ref, no.sobol_normal_base_samples_nd(S, len(Xt) + 1, m, seed)).values(X[EDGE_ROWS])
+    held = ~dup & (EDGE_ROWS != masked)
+    assert np.isfinite(so[held]).all() and held.sum() >= 60 and held[-1]
+    dev = np.abs(sg[EDGE_ROWS] - so)[held]
+    tag = f"m={m},signs={'mixed' if (signs < 0).any() else 'max'},S={S}"
+    print(f"{tag}: max |device - oracle| over {held.sum()} rows = {dev.max():.3e}")
+    record_deviation(f"qlognehvi_scores_slice_edges[{tag}]", dev.max(), NEHVI_ATOL)
+    assert np.allclose(sg[EDGE_ROWS][held], so[held], rtol=0, atol=NEHVI_ATOL), dev.max()
+
+
+def test_one_slice_equals_the_default_slicing():
+    """S = 33: ``BBH_NEHVI_SLICES=1`` (one thread adds all 33 samples) against the default four slices.  The terms are non-negative,
+    so two summation orders of S <= 64 terms differ by at most 2 (S - 1) 2^-53 < 1.5e-14 relative in the sum - the same absolute
+    amount in its logarithm; held to 1e-13."""
+    import torch
+
+    m = 3
+    X, Xt, signs, engines, models, ref, dup = _edge_problem(m, None)
+    Xd = torch.from_numpy(X).cuda()
+    out = []
+    for env in ({}, {"BBH_NEHVI_SLICES": "1"}):
+        hv = _scorer_under(env, engines, signs, Xt, ref, n_mc_samples=33, prune_baseline=False)
+        hv.prepare(11)
+        out.append(hv.score(Xd).cpu().numpy())
+    assert np.isfinite(out[0]).all() and np.isfinite(out[1]).all()
+    dev = np.abs(out[0] - out[1]).max()
+    print(f"one slice against four: max |difference| = {dev:.3e}")
+    assert dev <= 1e-13
+
+
+def test_a_target_without_conditional_means_is_refused():
+    """``bbh_qlognehvi_sm`` with one used target's ``tmat`` pointer null and N > 0: the bad-arguments error, nothing enqueued; the
+    next valid call on the same handle scores as the oracle says."""
+    import torch
+
+    from baybe_amd.engine import HipError
+    from baybe_amd.nehvi import HipNEHVI
+    from oracle import nehvi_oracle as no
+
+    m, S, seed = 2, 33, 11
+    X, Xt, signs, engines, models, ref, dup = _edge_problem(m, [1.0, -1.0])
+    Xd = torch.from_numpy(X).cuda()
+    hv = HipNEHVI(engines, signs, Xt, ref, n_mc_samples=S, prune_baseline=False)
+    hv.prepare(seed)
+    hv.cell_off, hv.cell_lo, hv.cell_ll = hv.cells()  # the host-cell entry point on the same cells
+    hv._cells_on_device = False
+    score_cells = hv._score_cells
+
+    def without_a_target(N, tp, vp, alive, scores):
+        tp[1] = None
+        return score_cells(N, tp, vp, alive, scores)
+
+    hv._score_cells = without_a_target
+    with pytest.raises(HipError, match="bbh_qlognehvi: bad arguments"):
+        hv.score(Xd)
+    hv._score_cells = score_cells
+    sg = hv.score(Xd).cpu().numpy()[EDGE_ROWS]
+    so = no.NEHVIOracle(models, signs, Xt, ref, no.sobol_normal_base_samples_nd(S, len(Xt) + 1, m, seed)).values(X[EDGE_ROWS])
+    assert np.allclose(sg[~dup], so[~dup], rtol=0, atol=NEHVI_ATOL), np.abs(sg - so)[~dup].max()

@@ -165,3 +165,46 @@ def test_recommend_through_the_plugin_surface():
     assert list(got.index) == list(exp.index[picks]), (list(got.index), picks)
     acq = rec.acquisition_values(exp.iloc[:50], space, obj, meas)
     assert np.isfinite(acq.to_numpy()).all() and (acq.to_numpy() >= 0).all()
+
+
+# ---- the sample-slice scaffold (csrc/bbh_slices.h) at its edges -------------------------------------------------------------------
+EDGE_ROWS = np.r_[0:60, 250:257]  # of N = 257: the second 256-row block of the scoring grid holds one row
+
+
+@pytest.mark.parametrize("S", [1, 9, 33])
+@pytest.mark.parametrize("m,signs", [(2, [1.0, -1.0]), (3, None)])
+def test_scores_match_the_restatement_at_the_slice_edges(m, signs, S):
+    """``bbh_qnehvi_kernel`` (fixed slices of 8 samples) and the shared finish kernel at N = 257 (two blocks of candidates): S = 1 is
+    less than one slice, S = 9 and S = 33 leave one sample in the last slice.  Rows 0 ... 59 and 250 ... 256 against the restatement
+    under the tolerance rule of this module (rows coinciding with a baseline row excluded); one compared row is masked and scores
+    -inf.  From S = 9 on at least one compared reference score is non-zero (an all-zero comparison would pass a kernel that adds
+    nothing)."""
+    import torch
+
+    from baybe_amd.nehvi import HipNEHVIPlain, compute_ref_point
+    from conftest import record_deviation
+
+    X, Xt, Y, signs, engines, models = setup(m, signs, N=257)
+    obj = Y * signs[None, :]
+    ref_point = compute_ref_point(obj)
+    atol = 1e-9 * float(np.prod(obj.max(0) - ref_point))
+    seed = 11
+    dup = coincides_with_baseline(X[EDGE_ROWS], Xt)
+    masked = int(EDGE_ROWS[~dup][3])
+    held = ~dup & (EDGE_ROWS != masked)
+    so = ref.qnehvi_scores(models, signs, Xt, ref_point, ref.base_samples(S, len(Xt), m, seed), X[EDGE_ROWS])
+    tag = f"{_tag(m, signs)},S={S}"
+    print(f"{tag}: {(so[held] > 0).sum()} of {held.sum()} compared reference scores are non-zero")
+    assert held.sum() >= 60 and held[-1] and np.isfinite(so).all()
+    assert S < 9 or (so[held] > 0).sum() >= 1
+    hv = HipNEHVIPlain(engines, signs, Xt, ref_point, n_mc_samples=S, prune_baseline=False)
+    hv.prepare(seed)
+    alive = torch.ones(len(X), dtype=torch.uint8, device="cuda")
+    alive[masked] = 0
+    sg = hv.score(torch.from_numpy(X).cuda(), alive).cpu().numpy()
+    assert np.isneginf(sg[masked]) and (np.delete(sg, masked) >= 0).all() and np.isfinite(np.delete(sg, masked)).all()
+    dev = np.abs(sg[EDGE_ROWS] - so)[held]
+    excess = (dev - RTOL * np.abs(so[held])).max()
+    print(f"{tag}: max |device - restatement| = {dev.max():.3e}, beyond rtol {excess:.3e} (atol {atol:.3e})")
+    record_deviation(f"qnehvi_scores_slice_edges_beyond_rtol[{tag}]", max(excess, 0.0), atol)
+    assert np.allclose(sg[EDGE_ROWS][held], so[held], rtol=RTOL, atol=atol), dev.max()
