@@ -14,7 +14,7 @@ def __getattr__(name):
     ``k_means`` / ``HipKMeansClusteringRecommender`` / ``gaussian_mixture`` / ``HipGaussianMixtureClusteringRecommender``
     (``baybe_amd.clustering``) and ``HipRandomForestSurrogate`` / ``make_baybe_forest_surrogate`` (``baybe_amd.forest``,
     ``baybe_amd.plugin``) and ``HipBayesianLinearSurrogate`` / ``make_baybe_linear_surrogate`` (``baybe_amd.linear``,
-    ``baybe_amd.plugin``), imported on first use: the modules pull in pandas and attrs, which a plain ``import baybe_amd`` does
+    ``baybe_amd.plugin``) and ``HipSHAPInsight`` / ``shapley_values`` (``baybe_amd.insights``), imported on first use: the modules pull in pandas and attrs, which a plain ``import baybe_amd`` does
     not need."""
     if name in ("farthest_point_sampling", "HipFPSRecommender"):
         from baybe_amd import sampling
@@ -41,11 +41,15 @@ def __getattr__(name):
         from baybe_amd import plugin
 
         return plugin.make_baybe_linear_surrogate
+    if name in ("HipSHAPInsight", "shapley_values"):
+        from baybe_amd import insights
+
+        return getattr(insights, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 __all__ = ["HipError", "HipUnavailableError", "is_available", "library_path", "farthest_point_sampling", "HipFPSRecommender", "k_medoids",
            "HipPAMClusteringRecommender", "k_means", "HipKMeansClusteringRecommender", "gaussian_mixture",
            "HipGaussianMixtureClusteringRecommender", "HipRandomForestSurrogate", "make_baybe_forest_surrogate",
-           "HipBayesianLinearSurrogate", "make_baybe_linear_surrogate"]
+           "HipBayesianLinearSurrogate", "make_baybe_linear_surrogate", "HipSHAPInsight", "shapley_values"]
 __version__ = "0.1.0"

@@ -193,6 +193,12 @@ SIGNATURES = {
     "bbh_nipv_gain": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, c_double_p, c_double_p, C.c_void_p,
                                 C.c_void_p]),
     "bbh_last_nipv_form": (C.c_int, [C.c_void_p]),
+    "bbh_shap_values": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_int32),
+                                  C.c_int32, C.c_void_p, C.c_void_p, c_double_p]),
+    "bbh_shap_compose": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_int32),
+                                   C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_void_p]),
+    "bbh_shap_reduce": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    "bbh_shap_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
     "bbh_analytic_acq": (
         C.c_int,
         [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_int32,

@@ -49,6 +49,7 @@ static bbh_switches bbh_read_switches() {
       {"BBH_EHVI_SLICE", INT, 0, nullptr, &S::ehvi_slice},
       {"BBH_NIPV_TILE", INT, 0, nullptr, &S::nipv_tile},
       {"BBH_NIPV_SLICE", INT, 0, nullptr, &S::nipv_slice},
+      {"BBH_SHAP_CPT", INT, 0, nullptr, &S::shap_cpt},
       {"BBH_NEI_FUSED", NOT, '0', &S::nei_fused, nullptr},
       {"BBH_SELECT", NOT, '0', &S::select_on, nullptr},
       {"BBH_SELECT_MAPPED", NOT, '0', &S::select_mapped, nullptr},

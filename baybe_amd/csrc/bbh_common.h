@@ -219,6 +219,7 @@ struct bbh_switches {
   int ehvi_slice = INT_MIN;       // BBH_EHVI_SLICE: MC samples per slice of the qEHVI / qLogEHVI kernels, 0 = all in one slice (unset: 16; A/B)
   int nipv_tile = 16;             // BBH_NIPV_TILE=32: two 16-candidate row tiles per workgroup of the qNIPV gain kernel instead of one (A/B: measured slower, KERNELS.md 4.15; falls back to one where 32 rows do not fit the LDS)
   int nipv_slice = 512;           // BBH_NIPV_SLICE: integration-point columns per slice of the qNIPV gain kernel, 0 = all in one slice (A/B)
+  int shap_cpt = 0;               // BBH_SHAP_CPT=1|4: coalitions per thread of the fused Shapley kernel (unset: 4 once that still leaves two workgroups per CU, else 1; A/B)
   bool nei_fused = true;          // BBH_NEI_FUSED=0: qNEI / qLogNEI through bbh_posterior_columns_sm + bbh_nei_q1 instead of the fused scoring pass (A/B, verification)
   bool select_on = true;          // BBH_SELECT=0: top-k / argmax by k rounds of workgroup argmax (A/B)
   bool select_mapped = true;      // BBH_SELECT_MAPPED=0: selection results through a device buffer + copy instead of host-mapped stores (A/B)

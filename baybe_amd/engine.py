@@ -951,6 +951,67 @@ class HipGP:
         """Row tiles per workgroup of the last ``nipv_gain`` launch: 0 one (16 candidates), 1 two (32), -1 none yet."""
         return int(self._lib.bbh_last_nipv_form(self._h))
 
+    # ---- exact Shapley values of the posterior mean (baybe_amd/insights.py) ----------------
+    SHAP_CHUNK_BYTES = 64 << 20  # composed rows one posterior pass of the generic form takes (at least one coalition's B rows)
+
+    def shap_values(self, X, background, groups, form: str = "auto", want_v: bool = False, n_groups: int | None = None):
+        """Exact interventional Shapley values of the posterior mean (``include/baybe_hip.h``): ``X`` [R, d] explained rows,
+        ``background`` [B, d], ``groups`` [d] the feature (0 .. M - 1) each comp-rep column belongs to, -1 for a column in no feature
+        (it keeps the background's value); ``n_groups`` = M where the last features own no column.  ``form``: ``"fused"``
+        (``bbh_shap_values``: one stationary kernel, one task, n <= 512; refused with the kernel's text elsewhere), ``"composed"``
+        (``bbh_shap_compose`` -> this engine's ``posterior`` -> ``bbh_shap_reduce`` -> ``bbh_shap_apply``: every model), ``"auto"``
+        (fused where it applies).  Returns ``(phi [R, M] device tensor, base_value, v [R, 2^M] device tensor or None)``; bit g of a
+        coalition's index stands for feature g.  ``shap_last_form`` names the form that answered."""
+        if form not in ("auto", "fused", "composed"):
+            raise ValueError(f"form must be 'auto', 'fused' or 'composed', not {form!r}")
+        torch = self._torch()
+        d = int(self.spec.d) if self.spec is not None else int(self.d)
+        X, Bg = self._as_dev(X), self._as_dev(background)
+        R, B = int(X.shape[0]), int(Bg.shape[0])
+        grp = np.ascontiguousarray(groups, dtype=np.int32).reshape(-1)
+        if grp.shape[0] != d:
+            raise ValueError(f"groups must name the feature of each of the {d} comp-rep columns")
+        M = int(n_groups) if n_groups is not None else int(grp.max(initial=-1)) + 1
+        if R < 1 or B < 1:
+            raise ValueError("need at least one explained row and one background row")
+        gp = grp.ctypes.data_as(C.POINTER(C.c_int32))
+        fits = 1 <= M <= 16  # (beyond that the library refuses, before any device work: nothing of size 2^M is allocated here)
+        phi = torch.empty((R, max(M, 1)), dtype=torch.float64, device=X.device)
+        v = torch.empty((R, 1 << M), dtype=torch.float64, device=X.device) if fits else None
+        if form == "fused" and self.spec is None:  # (a forest / linear engine: its handle holds no GP model of its own)
+            raise HipError("bbh_shap_values failed (-1): the fused form needs a Gaussian process model; this engine answers through "
+                           "form='composed'")
+        if form != "composed" and self.spec is not None:
+            base = C.c_double(0.0)
+            rc = self._lib.bbh_shap_values(self._h, X.data_ptr(), R, X.stride(0), Bg.data_ptr(), B, Bg.stride(0), gp, M,
+                                           v.data_ptr() if (fits and want_v) else None, phi.data_ptr(), C.byref(base))
+            if rc == 0:
+                self._shap_form = "fused"
+                return phi, float(base.value), (v if want_v else None)
+            msg = self._lib.bbh_last_error(self._h)
+            if form == "fused" or b"the fused form" not in (msg or b""):
+                self._check(rc, "bbh_shap_values")
+        if not fits:  # the generic form's own refusal text
+            self._check(self._lib.bbh_shap_compose(self._h, X.data_ptr(), R, X.stride(0), Bg.data_ptr(), B, Bg.stride(0), gp, d, M, 0, 0,
+                                                   None), "bbh_shap_compose")
+        pairs = R << M
+        per = max(1, int(self.SHAP_CHUNK_BYTES // (8 * B * d)))
+        vf = v.reshape(-1)
+        for p0 in range(0, pairs, per):
+            pc = min(per, pairs - p0)
+            rows = torch.empty((pc * B, d), dtype=torch.float64, device=X.device)
+            self._check(self._lib.bbh_shap_compose(self._h, X.data_ptr(), R, X.stride(0), Bg.data_ptr(), B, Bg.stride(0), gp, d, M, p0 * B,
+                                                   pc * B, rows.data_ptr()), "bbh_shap_compose")
+            mean = self.posterior(rows)[0].contiguous()
+            self._check(self._lib.bbh_shap_reduce(self._h, mean.data_ptr(), pc, B, vf[p0:p0 + pc].data_ptr()), "bbh_shap_reduce")
+        self._check(self._lib.bbh_shap_apply(self._h, v.data_ptr(), R, M, phi.data_ptr()), "bbh_shap_apply")
+        self._shap_form = "composed"
+        return phi, float(v[0, 0].item()), (v if want_v else None)
+
+    def shap_last_form(self):
+        """``"fused"`` or ``"composed"``: the form that answered the last ``shap_values``; None before the first."""
+        return getattr(self, "_shap_form", None)
+
     def analytic_acq(self, kind: str, mean, var, best_f: float = 0.0, sign: float = 1.0, beta: float = 0.2,
                      maximize: bool = True, alive=None):
         """Analytic acquisition values (PM, PSTD, UCB, EI, LogEI, PI) of N single candidates."""

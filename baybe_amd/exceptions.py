@@ -36,4 +36,15 @@ except Exception:  # noqa: BLE001
         """A model was used before being trained."""
 
 
+try:  # pragma: no cover - (older BayBE versions have no insights package)
+    from baybe.exceptions import IncompatibleExplainerError, NoMeasurementsError  # type: ignore
+except Exception:  # noqa: BLE001
+
+    class IncompatibleExplainerError(IncompatibilityError):
+        """An explainer is incompatible with the data it is presented."""
+
+    class NoMeasurementsError(Exception):
+        """A context expected measurements but none were available."""
+
+
 from baybe_amd.engine import ModelFittingError  # noqa: E402,F401

@@ -523,6 +523,28 @@ int bbh_nipv_gain(bbh_handle* h, const double* X_dev, int64_t N, int64_t ldx, co
                   const double* H_host, const double* ginv_host, const uint8_t* alive_dev, double* gain_dev);
 int bbh_last_nipv_form(bbh_handle* h); /* of the last bbh_nipv_gain launch: 0 one 16-row tile per workgroup, 1 two; -1 none yet */
 
+/* ---- Exact Shapley explanations of the posterior mean (baybe/insights/shap.py: SHAPInsight) ---------------------------------------
+ * M features = groups of comp-rep columns (group_of_col_host [d]: group index 0 .. M - 1, or -1 for a column in no group, which
+ * always keeps the background row's value), R explained rows X_dev [R, ldx], B background rows Bg_dev [B, ldb]:
+ *   v(r, S) = (1 / B) sum_b mean(compose(x_r on the groups of S, b elsewhere)),  mean = bbh_posterior's, original target scale,
+ *   phi_g(r) = sum_{S without g} |S|! (M - |S| - 1)! / M! [v(r, S + g) - v(r, S)],  base = v(., empty) = mean_b mean(b).
+ * Bit g of a mask S stands for group g.  1 <= M <= 16.
+ * bbh_shap_values: the fused form - one Matern-1/2, Matern-3/2, Matern-5/2 or RBF kernel, one task, n <= 512; anything else returns
+ * -1 and bbh_last_error names the unmet condition.  Per-group partial squared distances of the rows to the training points, then
+ * one kernel value per (r, S, b, t) with d2 = lo[S_lo] + hi[S_hi] from two tables of direct sums; no composed row is materialised.
+ * v_dev [R, 2^M] may be null (the handle's workspace holds it then); phi_dev [R, M]; base_host may be null.  Sums run over the
+ * training points ascending, then the background rows ascending, then the masks ascending: equal rows give equal bits wherever
+ * they stand, two runs give equal bits.
+ * bbh_shap_compose: the generic form's rows for ANY model with d columns (the handle needs no model): rows_dev [count, d] holds the
+ * composed rows of the triples first .. first + count of the order e = (r 2^M + S) B + b.
+ * bbh_shap_reduce: out_dev [pairs] = mean over b, ascending, of f_dev [pairs, B].   bbh_shap_apply: phi_dev [R, M] from v_dev [R, 2^M]. */
+int bbh_shap_values(bbh_handle* h, const double* X_dev, int64_t R, int64_t ldx, const double* Bg_dev, int64_t B, int64_t ldb,
+                    const int32_t* group_of_col_host, int32_t M, double* v_dev, double* phi_dev, double* base_host);
+int bbh_shap_compose(bbh_handle* h, const double* X_dev, int64_t R, int64_t ldx, const double* Bg_dev, int64_t B, int64_t ldb,
+                     const int32_t* group_of_col_host, int32_t d, int32_t M, int64_t first, int64_t count, double* rows_dev);
+int bbh_shap_reduce(bbh_handle* h, const double* f_dev, int64_t pairs, int64_t B, double* out_dev);
+int bbh_shap_apply(bbh_handle* h, const double* v_dev, int64_t R, int32_t M, double* phi_dev);
+
 /* Box decomposition of the non-dominated region, one per MC sample (host code, no device work; BoTorch's
  * FastNondominatedPartitioning inside qLogNoisyExpectedHypervolumeImprovement, built at
  * baybe/acquisition/_builder.py:319-324).  obj_host [S, n, m] oriented baseline objective samples, ref_host [m].
