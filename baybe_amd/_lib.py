@@ -301,6 +301,7 @@ SIGNATURES = {
     "bbh_last_posterior_seeded": (C.c_int, [C.c_void_p]),
     "bbh_last_nei_form": (C.c_int, [C.c_void_p]),
     "bbh_last_fit_form": (C.c_int, [C.c_void_p]),
+    "bbh_last_factor_form": (C.c_int, [C.c_void_p]),
     "bbh_timing_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "bbh_timing_read": (C.c_int, [C.c_void_p, c_double_p, c_int64_p, C.c_int]),
     "bbh_timing_read_family": (C.c_int, [C.c_void_p, C.c_int32, c_double_p, c_int64_p, C.c_int]),

@@ -336,6 +336,7 @@ extern "C" int bbh_trim(bbh_handle* h, int64_t keep_bytes) {
 extern "C" int bbh_last_posterior_form(bbh_handle* h) { return h ? h->last_form : -1; }
 extern "C" int bbh_last_posterior_seeded(bbh_handle* h) { return h ? (h->last_form == 1 && h->last_seeded) : -1; }
 extern "C" int bbh_last_fit_form(bbh_handle* h) { return h ? h->last_fit_form : -1; }
+extern "C" int bbh_last_factor_form(bbh_handle* h) { return h ? h->last_factor_form : -1; }
 
 extern "C" int bbh_timing_enable(bbh_handle* h, int enable) {
   if (!h) return -1;

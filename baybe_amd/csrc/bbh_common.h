@@ -355,6 +355,7 @@ struct bbh_handle {
   int last_seeded = 0;            // the last cooperative launch (last_form == 1) was the seeded one: bbh_last_posterior_seeded
   int last_form = -1;             // bbh_last_posterior_form
   int last_fit_form = -1;         // bbh_last_fit_form (enum bbh_fit_form)
+  int last_factor_form = -1;      // bbh_last_factor_form: 0 per-step launches, 1 tile-dataflow launch (the last attempt of bbh_factorize)
   int last_nei_form = -1;         // bbh_last_nei_form: 1 fused (bbh_score_nei), 2 unfused (bbh_nei_q1)
   int last_linear_form = -1;      // bbh_linear_last_form: 1 register, 2 block (bbh_linear_moments)
   int last_des_form = -1;         // bbh_desirability_last_form: 0 LDS, 1 workspace (bbh_desirability_pending)

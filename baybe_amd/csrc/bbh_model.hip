@@ -1039,6 +1039,7 @@ extern "C" int bbh_factorize(bbh_handle* h, const double* theta_host, double* ji
       jitter_latent = step;
     }
   }
+  h->last_factor_form = h->potrf_tiles_ran ? 1 : 0;  // (of the last attempt; a give-up of the tile-dataflow launch shows as 0)
   if (info != 0) {
     h->err = "bbh_factorize: train covariance not positive definite (even with jitter 1e-6)";
     return -4;

@@ -1550,6 +1550,11 @@ class HipGP:
         return {0: "launch", 1: "small", 2: "tiles+mt", 3: "tiles+mt-partial", 4: "tiles", 5: "gram+tiles", 6: "one-launch",
                 7: "split", 8: "rff", 9: "steps+tail"}.get(self._lib.bbh_last_fit_form(self._h), "none")
 
+    def factorization_form(self) -> str:
+        """How the last ``factorize`` (its last attempt) factorised the train covariance: ``"steps"`` - per-step launches - or
+        ``"tiles"`` - the one-launch tile-dataflow factorisation; ``"none"`` before the first one."""
+        return {0: "steps", 1: "tiles"}.get(self._lib.bbh_last_factor_form(self._h), "none")
+
     def timing(self, enable, families=None):
         """HIP-event timing of the kernel families on / off; ``families`` (names as for ``timing_read``) restricts the events to those
         families - an event between two back-to-back kernels costs the stream ~5 us."""

@@ -827,6 +827,10 @@ enum bbh_fit_form {
   BBH_FIT_FORM_STEPS_TAIL = 9        /* Gram launch, per-step factorisation launches, dataflow tail */
 };
 int bbh_last_fit_form(bbh_handle* h);
+/* How the last bbh_factorize factorised the train covariance (its last attempt): 0 per-step launches (one diagonal-block kernel,
+ * panel and trailing update per block row), 1 the one-launch tile-dataflow factorisation (np <= 1024 while its tiles are co-resident);
+ * -1 before the first factorisation of a kernel-space model. */
+int bbh_last_factor_form(bbh_handle* h);
 enum bbh_timed_family {
   BBH_TIMED_POSTERIOR = 0, BBH_TIMED_CROSS = 1, BBH_TIMED_PENDING = 2,
   BBH_TIMED_COLUMNS = 3,  /* bbh_posterior_columns: conditional means under S target columns (qLogNEHVI) */
