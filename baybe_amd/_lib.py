@@ -199,6 +199,10 @@ SIGNATURES = {
                                    C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_void_p]),
     "bbh_shap_reduce": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
     "bbh_shap_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
+    "bbh_polytope_sample": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
+                                      c_double_p, c_double_p, c_double_p, C.c_int64, C.c_int32, C.c_uint64, C.c_void_p]),
+    "bbh_polytope_project": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, c_double_p, c_double_p, c_double_p, c_double_p,
+                                       C.c_double, C.c_double, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
     "bbh_analytic_acq": (
         C.c_int,
         [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_int32,

@@ -1008,6 +1008,47 @@ class HipGP:
         self._shap_form = "composed"
         return phi, float(v[0, 0].item()), (v if want_v else None)
 
+    def polytope_sample(self, reduced: dict, R: int, T: int, seed: int):
+        """``R`` uniform samples [R, dc] (device tensor) of a polytope given by its reduced set (``Polytope.reduced()``): one
+        hit-and-run chain of ``T`` steps per sample, counter-based uniforms from ``seed`` (``bbh_polytope_sample``)."""
+        torch = self._torch()
+        a = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in reduced.items()}
+        dc, dz = a["Z"].shape
+        mi = a["bg"].shape[0]
+        out = torch.empty((int(R), dc), dtype=torch.float64, device=self._dev())
+
+        def p(name):
+            return a[name].ctypes.data_as(_lib.c_double_p)
+
+        self._check(self._lib.bbh_polytope_sample(self._h, dc, dz, mi, p("Z"), p("GZ"), p("c0"), p("lo"), p("hi"), p("bl"), p("bu"), p("bg"),
+                                                  int(R), int(T), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), out.data_ptr()),
+                    "bbh_polytope_sample")
+        return out
+
+    def polytope_project(self, P, lo, hi, rows, rhs, me: int, tolf: float, mu_min: float):
+        """Euclidean projection of every row of ``P`` [k, dc] onto {lo <= c <= hi, rows[:me] c = rhs[:me], rows[me:] c >= rhs[me:]}:
+        ``(out [k, dc], status [k] int32)`` device tensors; status 1 = iteration budget exhausted (``bbh_polytope_project``)."""
+        torch = self._torch()
+        if isinstance(P, np.ndarray):
+            P = torch.from_numpy(np.ascontiguousarray(P, dtype=np.float64))
+        P = P.to(self._dev(), dtype=torch.float64)
+        if P.dim() != 2 or P.stride(1) != 1:
+            P = P.reshape(-1, len(lo)).contiguous()
+        lo, hi, rows, rhs = (np.ascontiguousarray(v, dtype=np.float64) for v in (lo, hi, rows, rhs))
+        dc = lo.shape[0]
+        m = rhs.shape[0]
+        k = int(P.shape[0])
+        out = torch.empty((k, dc), dtype=torch.float64, device=P.device)
+        status = torch.empty(k, dtype=torch.int32, device=P.device)
+
+        def p(arr):
+            return arr.ctypes.data_as(_lib.c_double_p)
+
+        self._check(self._lib.bbh_polytope_project(self._h, dc, int(me), m - int(me), p(rows), p(rhs), p(lo), p(hi), float(tolf), float(mu_min),
+                                                   P.data_ptr(), k, P.stride(0) if k > 1 else max(P.stride(0), dc), out.data_ptr(),
+                                                   status.data_ptr()), "bbh_polytope_project")
+        return out, status
+
     def shap_last_form(self):
         """``"fused"`` or ``"composed"``: the form that answered the last ``shap_values``; None before the first."""
         return getattr(self, "_shap_form", None)

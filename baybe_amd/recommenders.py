@@ -223,11 +223,26 @@ def _nipv_kernel_refusal(surrogate, searchspace):
     return None
 
 
+def _polytope_of(cont):
+    """The ``Polytope`` of a continuous subspace that carries linear constraints (None: it has none).  Building it checks what the
+    device-side sampler and projection take - row and column limits, no interpoint rows, a set with interior - and raises an
+    ``IncompatibilityError`` naming the alternative otherwise."""
+    if not any(len(getattr(cont, name, ()) or ()) for name in ("constraints_lin_eq", "constraints_lin_ineq")):
+        return None
+    from baybe_amd.polytope import Polytope
+
+    return Polytope.from_subspace(cont)
+
+
 def _check_continuous_part(cont, optimizer: str = "compass") -> None:
-    """What of ``SubspaceContinuous`` the HIP path's search handles: box-bounded parameters.  Linear / nonlinear / cardinality /
-    interpoint constraints need the reference's constrained optimiser.  ``optimizer``: the recommender's ``continuous_optimizer``."""
+    """What of ``SubspaceContinuous`` the HIP path's search handles: box-bounded parameters, and under
+    ``continuous_optimizer="gradient"`` linear equality / inequality constraints on them (``baybe_amd.polytope``).  Nonlinear /
+    cardinality / interpoint constraints need the reference's constrained optimiser.  ``optimizer``: the recommender's
+    ``continuous_optimizer``."""
     for name in ("constraints_lin_eq", "constraints_lin_ineq", "constraints_nonlin", "constraints_cardinality"):
         if len(getattr(cont, name, ()) or ()):
+            if optimizer == "gradient" and name in ("constraints_lin_eq", "constraints_lin_ineq"):
+                continue
             raise IncompatibilityError(
                 f"The continuous subspace carries '{name}'; the HIP path searches box-bounded continuous parameters only. "
                 f"Use BotorchRecommender."
@@ -238,6 +253,7 @@ def _check_continuous_part(cont, optimizer: str = "compass") -> None:
             raise IncompatibilityError(
                 f"{dc} continuous parameters: continuous_optimizer='gradient' differentiates up to {MAX_GRADIENT_CONTINUOUS} of them "
                 f"on the device; use BotorchRecommender beyond that.")
+        _polytope_of(cont)  # (before anything is fitted: more than 16 rows, an interpoint row, an empty set)
         return
     if dc > MAX_HYBRID_CONTINUOUS:  # (before anything is fitted)
         raise IncompatibilityError(
@@ -898,11 +914,18 @@ class HipRecommenderImpl:
         # with the continuous dimension (512 per dimension) where the row budget allows, and beyond the dimension the
         # search was validated for (tests/test_hybrid_gpu.py: d_c <= 6) it says so
         R = int(max(1, min(max(self.n_raw_samples, 512 * dc), 4_000_000 // max(Nd, 1))))
-        sob = torch.quasirandom.SobolEngine(dimension=max(dc, 1), scramble=True, seed=self._sampler_seed())
-        U = sob.draw(R, dtype=torch.float64).numpy()[:, :dc]
-        Craw = cb[0] + U * (cb[1] - cb[0])
         dev = eng._dev()
-        Dd, Cd = torch.from_numpy(D).to(dev), torch.from_numpy(np.ascontiguousarray(Craw)).to(dev)
+        poly = _polytope_of(cont) if gradient else None
+        if poly is not None:
+            # linear constraints: the raw samples are uniform in the polytope, one hit-and-run chain each (bbh_polytope_sample; the
+            # reference: get_polytope_samples through SubspaceContinuous.sample_uniform, searchspace/continuous.py:544-571)
+            Cd = poly.sample(eng, R, seed=self._sampler_seed())
+        else:
+            sob = torch.quasirandom.SobolEngine(dimension=max(dc, 1), scramble=True, seed=self._sampler_seed())
+            U = sob.draw(R, dtype=torch.float64).numpy()[:, :dc]
+            Craw = cb[0] + U * (cb[1] - cb[0])
+            Cd = torch.from_numpy(np.ascontiguousarray(Craw)).to(dev)
+        Dd = torch.from_numpy(D).to(dev)
         X = torch.cat([Dd.repeat_interleave(R, dim=0), Cd.repeat(Nd, 1)], dim=1).contiguous()  # row i R + r = [disc i | cont r]
         base = self._pending_comp if self._pending_comp is not None else np.zeros((0, dd + dc))
         seed = self._sampler_seed()
@@ -912,7 +935,7 @@ class HipRecommenderImpl:
             pend = np.vstack([base] + picks) if picks else base
             scores = self._mc_or_analytic(eng, acqf, X, mean, var, pend, seed, self._sign(surrogate))
             if gradient:
-                best_row = self._gradient_refine(eng, acqf, X, scores, Nd, R, dd, cb, pend, seed, self._sign(surrogate))
+                best_row = self._gradient_refine(eng, acqf, X, scores, Nd, R, dd, cb, pend, seed, self._sign(surrogate), poly)
                 picks.append(best_row.reshape(1, -1))
                 if has_disc:
                     pick_labels.append(labels[int(np.nonzero((D == best_row[:dd]).all(axis=1))[0][0])])
@@ -960,15 +983,17 @@ class HipRecommenderImpl:
             return self._analytic_scores(eng, acqf, mean, var, sign)
         return self._mc_scores_with_pending(eng, acqf, X, mean, var, pend, seed, sign)
 
-    def _gradient_refine(self, eng, acqf, X, scores, Nd: int, R: int, dd: int, cb: np.ndarray, pend, seed, sign):
+    def _gradient_refine(self, eng, acqf, X, scores, Nd: int, R: int, dd: int, cb: np.ndarray, pend, seed, sign, poly=None):
         """Gradient-based refinement of one greedy step.  Starts as the reference chooses them, per discrete row its ``n_restarts``
         best raw samples (``optimize_acqf_mixed`` runs ``optimize_acqf`` per fixed-feature dictionary), restricted to the rows with
         the best raw score so that at most ``MAX_GRADIENT_STARTS`` starts advance together; all of them climb qLogEI in their
-        continuous coordinates in ``maximize_box``, one device pass (``qlogei_value_grad``) per trial.  Returns the best final row
-        and leaves starts, final points and values on ``_last_continuous_trace``."""
+        continuous coordinates in ``maximize_box``, one device pass (``qlogei_value_grad``) per trial.  With linear constraints
+        (``poly``) they climb in ``maximize_polytope``, the device projection (``bbh_polytope_project``) standing where the box
+        optimiser clips.  Returns the best final row and leaves starts, final points, values and the number of projection calls on
+        ``_last_continuous_trace``."""
         import torch
 
-        from baybe_amd.continuous import maximize_box
+        from baybe_amd.continuous import maximize_box, maximize_polytope
 
         if len(pend) > _lib.MAX_PENDING:
             raise IncompatibilityError(
@@ -995,15 +1020,20 @@ class HipRecommenderImpl:
             val, grad, ok = eng.qlogei_value_grad(Xc, cols, z, self._best_f, sign)
             return val.cpu().numpy(), grad.cpu().numpy(), ok.cpu().numpy()
 
+        project = poly.projector(eng) if poly is not None else None
         try:
-            res = maximize_box(value_and_grad, starts[:, dd:], cb[0], cb[1])
+            if project is not None:
+                res = maximize_polytope(value_and_grad, starts[:, dd:], project)
+            else:
+                res = maximize_box(value_and_grad, starts[:, dd:], cb[0], cb[1])
         finally:
             eng.set_pending(None)
         final = np.hstack([starts[:, :dd], res.x])
         vals = np.where(np.isfinite(res.values), res.values, -np.inf)
         i = int(np.argmax(vals))
         self._last_continuous_trace.append({"starts": starts, "final": final, "values": res.values.copy(), "best": i,
-                                            "iterations": res.iterations, "calls": res.calls})
+                                            "iterations": res.iterations, "calls": res.calls,
+                                            "projections": project.calls if project is not None else 0})
         return final[i]
 
     def _compass_refine(self, eng, acqf, starts: np.ndarray, dd: int, cb: np.ndarray, pend, seed, sign, iters: int = 24):
@@ -1255,7 +1285,7 @@ def recommender_fields(with_base_fields: bool = True, surrogate_factory=HipGauss
         "_nehvi": field(default=None, init=False, eq=False, repr=False),
         "_acqf_in_use": field(default=None, init=False, eq=False, repr=False),
         "_program": field(default=None, init=False, eq=False, repr=False),  # ObjectiveProgram of a transformed single target, or a DesirabilityProgram
-        # per greedy step of the last hybrid / continuous recommendation under "gradient": starts, final points, values (tests, timing)
+        # per greedy step of the last hybrid / continuous recommendation under "gradient": starts, final points, values, projection calls (tests, timing)
         "_last_continuous_trace": field(default=None, init=False, eq=False, repr=False),
     }
     if with_base_fields:

@@ -182,6 +182,28 @@ def farthest_point_sampling(points: np.ndarray, n_samples: int = 1, initializati
 _points_factory = DevicePoints
 
 
+def polytope_samples(bounds, equality_constraints=None, inequality_constraints=None, n: int = 1, n_steps: int | None = None,
+                     seed: int | None = None, device: int = 0) -> np.ndarray:
+    """Uniform samples [n, dc] of the polytope ``{lo <= x <= hi, sum coeff x[idx] = rhs, sum coeff x[idx] >= rhs}`` in the argument
+    format of ``botorch.utils.sampling.get_polytope_samples`` - ``bounds`` [2, dc], ``(indices, coefficients, rhs)`` triples - which
+    is what ``SubspaceContinuous.sample_uniform`` asks BoTorch for (baybe/searchspace/continuous.py:544-571).  Instead of one
+    sequential hit-and-run chain (10 000 burn-in steps, thinning 32) every sample is the end of its own chain of ``n_steps`` steps
+    from the Chebyshev centre, all chains advancing together on the device (``bbh_polytope_sample``); ``n_steps`` defaults to
+    ``polytope.default_n_steps(dz)``.  The uniforms are counter-based: the same ``seed`` gives the same rows, and the first rows of
+    a larger call.  ``seed=None`` draws one from torch's global generator, as the MC samplers of the recommenders do."""
+    from baybe_amd.engine import HipGP, draw_sampler_seed
+    from baybe_amd.polytope import Polytope
+
+    if int(n) < 0:
+        raise ValueError(f"The number of requested samples must be non-negative. Provided: {n=}.")
+    poly = Polytope.from_botorch(bounds, equality_constraints, inequality_constraints)
+    gp = HipGP(device)
+    try:
+        return poly.sample(gp, int(n), n_steps, draw_sampler_seed() if seed is None else int(seed)).cpu().numpy()
+    finally:
+        gp.close()
+
+
 def _convert_initialization(value) -> str:
     """``FPSInitialization`` (nonpredictive/sampling.py:77-84) by value or member."""
     name = str(getattr(value, "value", value))

@@ -545,6 +545,34 @@ int bbh_shap_compose(bbh_handle* h, const double* X_dev, int64_t R, int64_t ldx,
 int bbh_shap_reduce(bbh_handle* h, const double* f_dev, int64_t pairs, int64_t B, double* out_dev);
 int bbh_shap_apply(bbh_handle* h, const double* v_dev, int64_t R, int32_t M, double* phi_dev);
 
+/* ---- Linear constraints of a continuous subspace (baybe/constraints/continuous.py: ContinuousLinearConstraint) ---------------------
+ * The feasible set { c in R^dc : lo <= c <= hi, E c = e, G c >= g }, dc <= 32, me + mi <= 16 rows (dependent equalities dropped by
+ * the caller).  Neither call needs a model on the handle.  Nothing is contracted and every sum runs over the columns, then the
+ * rows, ascending; no transcendental function is used.
+ * bbh_polytope_sample replaces botorch.utils.sampling.get_polytope_samples (baybe/searchspace/continuous.py:544-571, one sequential
+ * hit-and-run chain with 10 000 burn-in steps): R independent hit-and-run chains of T steps in the reduced coordinates c = c0 + Z y
+ * (Z_host [dc, dz] an orthonormal basis of null(E), c0 an interior point), every chain from y = 0, over the rows
+ * bl <= Z y <= bu (bl = lo - c0, bu = hi - c0) and GZ y >= bg (GZ_host [mi, dz] = G Z, bg = g - G c0).  One step: d = u - 1/2 with
+ * u uniform in [0, 1)^dz, the chord by a ratio test with slacks recomputed from y, t uniform on the chord.  The uniforms are
+ * counter-based (SplitMix64's finaliser): key = mix(mix(seed + G) + G (chain + 1)), h = mix(key + G (64 step + draw + 1)),
+ * u = (h >> 11) 2^-53, G = 0x9E3779B97F4A7C15 - a pure function of (seed, chain, step, draw), so the same seed gives the same bits
+ * however the chains are spread over the grid, and chain r of a call for R rows is chain r of any larger call.
+ * out_dev [R, dc] = clip(c0 + Z y, lo, hi).  1 <= dz <= dc (dz = 0 - the equalities pin the point - is the caller's to answer).
+ * bbh_polytope_project stands where the box optimiser clips (np.clip in baybe_amd/continuous.py::maximize_box; the reference hands
+ * its constraints to scipy's SLSQP inside botorch's optimize_acqf): out_dev [k, dc] = the Euclidean projection of every row of
+ * P_dev [k, ldp] by a regularised semismooth Newton ascent on the dual in the me + mi multipliers, the box applied as a clip.
+ * R_host [me + mi, dc] = [E; G], t_host = [e; g].  status_dev [k]: 0 ok, 1 iteration budget exhausted (the row holds the clipped
+ * point of the last multipliers).  The output lies in [lo, hi] bit-exactly and meets |E x - e|_i, (g - G x)_i^+ <= tolf S_abs,i,
+ * S_abs,i = sum_k |row_ik x_k| + |rhs_i|; callers pass tolf = 4 (dc + 2 dc + mi) eps.  A row that already meets this comes back
+ * bit for bit (so projecting twice changes nothing); equal rows give equal bits wherever they stand; two runs give equal bits.
+ * mu_min: the smallest regulariser, 1e-10 max_i |row_i|^2. */
+int bbh_polytope_sample(bbh_handle* h, int32_t dc, int32_t dz, int32_t mi, const double* Z_host, const double* GZ_host,
+                        const double* c0_host, const double* lo_host, const double* hi_host, const double* bl_host,
+                        const double* bu_host, const double* bg_host, int64_t R, int32_t T, uint64_t seed, double* out_dev);
+int bbh_polytope_project(bbh_handle* h, int32_t dc, int32_t me, int32_t mi, const double* R_host, const double* t_host,
+                         const double* lo_host, const double* hi_host, double tolf, double mu_min, const double* P_dev, int64_t k,
+                         int64_t ldp, double* out_dev, int32_t* status_dev);
+
 /* Box decomposition of the non-dominated region, one per MC sample (host code, no device work; BoTorch's
  * FastNondominatedPartitioning inside qLogNoisyExpectedHypervolumeImprovement, built at
  * baybe/acquisition/_builder.py:319-324).  obj_host [S, n, m] oriented baseline objective samples, ref_host [m].
