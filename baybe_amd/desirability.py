@@ -20,11 +20,14 @@ from types import SimpleNamespace
 import numpy as np
 
 from baybe_amd.engine import GreedyResult, draw_sampler_seed, sobol_normal_base_samples
-from baybe_amd.exceptions import IncompatibilityError
+from baybe_amd.exceptions import IncompatibilityError, IncompatibleAcquisitionFunctionError
 from baybe_amd.objective import MAX_OPS, ObjectiveProgram, _fold, _walk
+from baybe_amd.scoring import check_joint_batch, refuse_shard
 
 MAX_TARGETS = 8  # BBH_DES_MAX_TARGETS
 SCALARIZERS = {"MEAN": 0, "GEOM_MEAN": 1}  # enum bbh_scalarizer
+SHARD_TEXT = ("Row shards are not on the HIP path of desirability objectives with one model per target; score them on one "
+              "device, or use 'DesirabilityObjective(as_pre_transformation=True)'.")
 EPS = 2.0**-52  # torch.finfo(float64).eps: the reference's guard inside the logarithm (objectives/desirability.py:62-64)
 
 
@@ -138,12 +141,13 @@ class HipDesirability:
     engine's ``desirability_acq``)."""
 
     def __init__(self, engines, program: DesirabilityProgram, X_all, kind: str = "qLogEI", n_mc_samples: int = 512, beta: float = 0.2,
-                 device: int = 0):
+                 device: int = 0, analytic: bool = False, maximize: bool = True):
         self.engines = list(engines)
         if len(self.engines) != program.n_targets:
             raise ValueError(f"{program.n_targets} targets need as many models, got {len(self.engines)}")
         self.outputs = [SimpleNamespace(engine=e, ext=e) for e in self.engines]
         self.program, self.kind, self.S, self.beta, self.device = program, kind, int(n_mc_samples), float(beta), int(device)
+        self.analytic, self.maximize = bool(analytic), maximize  # (an analytic ``kind`` reads the combined Gaussian moments)
         self.X_all = np.ascontiguousarray(np.atleast_2d(X_all), dtype=np.float64)
         self._best_f = None
 
@@ -237,3 +241,37 @@ class HipDesirability:
         finally:
             self._clear_pending()
         return GreedyResult(indices, values)
+
+    # ---- the recommender's surface (``baybe_amd.scoring``): ONE sampler seed per call, none for the analytic kinds ---------------
+    supports_continuous = False
+    check_request = staticmethod(check_joint_batch)
+
+    def _analytic_scores(self, X, alive=None):
+        """The analytic ``kind`` on the Gaussian desirability N(sum_t c_t mu_t + offset, sum_t c_t^2 sigma_t^2) of an arithmetic mean
+        of affine targets (``DesirabilityProgram.as_affine``; to_botorch_posterior_transform, objectives/desirability.py:266-320)."""
+        c, offset = self.program.as_affine()
+        mean = var = None
+        for ct, e in zip(c, self.engines):
+            m, v = e.posterior(X)
+            mean = ct * m + offset if mean is None else mean + ct * m
+            var = (ct * ct) * v if var is None else var + (ct * ct) * v
+        return self.engines[0].analytic_acq(self.kind, mean, var, self.best_f(), 1.0, self.beta, self.maximize, alive)
+
+    def select(self, X, q, *, seeds, X_pending=None, alive=None, shard=None) -> GreedyResult:
+        refuse_shard(shard, SHARD_TEXT)
+        if self.analytic:  # q = 1 by construction
+            val, idx = self.engines[0].argmax(self._analytic_scores(X, alive))
+            return GreedyResult([int(idx)], [float(val)])
+        return self.greedy(X, q, seed=seeds(), X_pending=X_pending, alive=alive)
+
+    def values(self, X, *, seeds, X_pending=None):
+        return self._analytic_scores(X) if self.analytic else self.score(X, X_pending=X_pending, seed=seeds())
+
+    def joint_value(self, batch, *, seeds, X_pending=None) -> float:
+        """The value of one q-batch (candidate = first row, the others enter as pending rows)."""
+        if self.analytic:
+            if len(batch) != 1 or X_pending is not None:
+                raise IncompatibleAcquisitionFunctionError("Analytic acquisition functions score single points only.")
+            return float(self._analytic_scores(batch).cpu().numpy()[0])
+        base = X_pending if X_pending is not None else np.zeros((0, batch.shape[1]))
+        return float(self.score(batch[:1], X_pending=np.vstack([batch[1:], base]), seed=seeds()).cpu().numpy()[0])

@@ -23,8 +23,14 @@ import numpy as np
 
 from baybe_amd.engine import GreedyResult, draw_sampler_seed, sobol_normal_base_samples
 from baybe_amd.exceptions import IncompatibilityError
+from baybe_amd.scoring import refuse_shard
 
 MAX_OBJECTIVES = 4  # BBH_MAX_OBJECTIVES
+
+
+def shard_text(name: str) -> str:
+    return (f"Row shards are not on the HIP path of '{name}'; score the candidates on one device, or use "
+            f"qLogNoisyExpectedHypervolumeImprovement.")
 
 
 def check_alpha(alpha) -> None:
@@ -152,12 +158,27 @@ class HipEHVI:
             if p:
                 self._clear_pending()
 
-    def joint_value(self, batch, X_pending=None, seed=None) -> float:
+    # ---- the recommender's surface (``baybe_amd.scoring``): ONE sampler seed per call ------------------------------------------
+    supports_continuous = False
+
+    @staticmethod
+    def check_request(batch_size, n_pend, acqf=None, program=None, model=None) -> None:
+        """The candidate, the pending experiments and the picks are ONE joint batch (no baseline to cache them into)."""
+        HipEHVI.check_batch(1 + n_pend + batch_size)
+
+    def select(self, X, q, *, seeds, X_pending=None, alive=None, shard=None) -> GreedyResult:
+        refuse_shard(shard, shard_text("qLogExpectedHypervolumeImprovement" if self.log else "qExpectedHypervolumeImprovement"))
+        return self.greedy(X, q, seed=seeds(), X_pending=X_pending, alive=alive)
+
+    def values(self, X, *, seeds, X_pending=None):
+        return self.score(X, X_pending=X_pending, seed=seeds())
+
+    def joint_value(self, batch, *, seeds, X_pending=None) -> float:
         """The value of the whole batch ``[batch ; X_pending]`` as one joint q-batch: its first point scored with the others pending
         (the inclusion-exclusion is symmetric in the points)."""
         batch = np.atleast_2d(np.asarray(batch, dtype=np.float64))
         rest = batch[1:] if X_pending is None or len(X_pending) == 0 else np.vstack([batch[1:], np.atleast_2d(X_pending)])
-        return float(self.score(batch[:1], X_pending=rest, seed=seed).cpu().numpy()[0])
+        return float(self.score(batch[:1], X_pending=rest, seed=seeds()).cpu().numpy()[0])
 
     def greedy(self, X, q: int, seed=None, X_pending=None, alive=None) -> GreedyResult:
         """Sequential greedy of ``optimize_acqf_discrete``: the m posterior passes once, then per step the picks' cross-covariances

@@ -32,6 +32,7 @@ from attrs import field
 
 from baybe_amd.engine import GreedyResult, HipGP
 from baybe_amd.exceptions import IncompatibilityError, IncompatibleSurrogateError, ModelNotTrainedError
+from baybe_amd.scoring import check_joint_batch, refuse_shard
 from baybe_amd.surrogates import (
     _availability_property,
     _frame_hash,
@@ -291,14 +292,18 @@ class HipForestEngine(HipGP):
 
 
 # ---- the acquisition scorer the recommender drives -----------------------------------------------------------------------------------
+def shard_text(name: str) -> str:
+    return f"Row shards are not on the HIP path of '{name}'; score the forest on one device."
+
+
 class HipForestAcq:
     """MC acquisition functions under the forest's ensemble posterior, in the slot and with the surface of the recommender's other
-    device scorers (``greedy`` / ``prepare`` / ``score``).  One sampler seed per recommendation; the greedy loop keeps the member
+    device scorers (``baybe_amd.scoring``, over ``greedy`` / ``prepare`` / ``score``).  One sampler seed per recommendation; the greedy loop keeps the member
     counts fixed across its steps (same sampler, same base samples), appends each pick's per-tree predictions to the pending block
     and masks the pick out; first-index argmax."""
 
     def __init__(self, surrogate, kind: str, sign: float, best_f: float, n_mc_samples: int, beta: float = 0.2):
-        self.outputs = [surrogate]
+        self.name = type(surrogate).__name__
         self.engine = surrogate.engine
         self.kind, self.sign, self.best_f, self.S, self.beta = kind, float(sign), float(best_f), int(n_mc_samples), float(beta)
         self._counts = self._order = self._pend = None
@@ -319,7 +324,7 @@ class HipForestAcq:
         return eng.forest_mc_acq(eng.forest, self.kind, eng._as_dev(Xd), self._counts, self._order, self.S, self._pend, self.best_f,
                                  self.sign, self.beta, alive)
 
-    def greedy(self, Xd, batch_size: int, seed: int, X_pending=None, alive=None, **_unused) -> GreedyResult:
+    def greedy(self, Xd, batch_size: int, seed: int, X_pending=None, alive=None) -> GreedyResult:
         eng = self.engine
         torch = eng._torch()
         Xd = eng._as_dev(Xd)
@@ -334,6 +339,24 @@ class HipForestAcq:
             self._pend = column if self._pend is None else torch.cat([self._pend, column], dim=1).contiguous()
             alive[int(idx)] = 0
         return GreedyResult(indices, values)
+
+    # ---- the recommender's surface (``baybe_amd.scoring``): ONE sampler seed per call (the posterior has no pruning draw) ---------
+    supports_continuous = False
+    check_request = staticmethod(check_joint_batch)
+
+    def select(self, X, q, *, seeds, X_pending=None, alive=None, shard=None) -> GreedyResult:
+        refuse_shard(shard, shard_text(self.name))
+        return self.greedy(X, q, seeds(), X_pending, alive)
+
+    def values(self, X, *, seeds, X_pending=None):
+        self.prepare(seeds(), X_pending)
+        return self.score(self.engine._as_dev(X))
+
+    def joint_value(self, batch, *, seeds, X_pending=None) -> float:
+        """Incremental: the value of the batch's last point with the others (and the pending rows) pending."""
+        rest = [batch[:-1]] + ([X_pending] if X_pending is not None else [])
+        self.prepare(seeds(), np.vstack(rest) if len(batch) > 1 or X_pending is not None else None)
+        return float(self.score(self.engine._as_dev(batch[-1:])).cpu().numpy()[0])
 
 
 # ---- the surrogate -----------------------------------------------------------------------------------------------------------------------

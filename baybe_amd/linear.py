@@ -37,6 +37,7 @@ from attrs import field
 from baybe_amd.engine import GreedyResult, HipGP, sobol_normal_base_samples
 from baybe_amd.exceptions import IncompatibilityError, IncompatibleSurrogateError, ModelNotTrainedError
 from baybe_amd.forest import _BOOL, _FLOAT, _INT, _matches, refuse_continuous
+from baybe_amd.scoring import HipSingleTargetAcq, refuse_shard
 from baybe_amd.surrogates import (
     _availability_property,
     _frame_hash,
@@ -54,6 +55,18 @@ AUTO_REGISTER_MAX_KEPT = 16  # ... and up to where form "auto" takes the registe
 
 JOINT_TEXT = ("cannot be used for joint posterior evaluation: its posterior is an independent Gaussian per point, so batches of more "
               "than one point and pending experiments are not supported (as for the reference's BayesianLinearSurrogate)")
+
+
+
+def refuse_joint(name: str, batch_size: int, n_pend: int) -> None:
+    """An independent Gaussian per point has no joint posterior (surrogates/base.py:484-503): one point, nothing pending."""
+    if batch_size != 1 or n_pend > 0:
+        raise IncompatibleSurrogateError(f"'{name}' {JOINT_TEXT}.")
+
+
+def shard_text(name: str) -> str:
+    return f"Row shards are not on the HIP path of '{name}'; score the linear model on one device."
+
 
 # ---- model_params: make_dict_validator(_ARDRegressionParams) without cattrs ---------------------------------------------------------
 _ARD_PARAMS = {  # linear.py:20-36
@@ -246,15 +259,14 @@ class HipLinearAcq:
     ``eng.mc_acq(kind, mean, var, z, ...)`` with ``sobol_normal_base_samples(S, 1, seed)``; first-index argmax."""
 
     def __init__(self, surrogate, kind: str, sign: float, best_f: float, n_mc_samples: int, beta: float = 0.2, objective=None):
-        self.outputs = [surrogate]
+        self.name = type(surrogate).__name__
         self.engine = surrogate.engine
         self.kind, self.sign, self.best_f, self.S, self.beta = kind, float(sign), float(best_f), int(n_mc_samples), float(beta)
         self.objective = objective
         self._z = None
 
     def prepare(self, seed: int, X_pending=None) -> None:
-        if X_pending is not None and len(X_pending):
-            raise IncompatibleSurrogateError(f"'{type(self.outputs[0]).__name__}' {JOINT_TEXT}.")
+        refuse_joint(self.name, 1, 0 if X_pending is None else len(X_pending))
         self._z = sobol_normal_base_samples(self.S, 1, seed)[:, 0]
 
     def score(self, Xd, alive=None):
@@ -263,12 +275,46 @@ class HipLinearAcq:
         okw = {} if self.objective is None else {"objective": self.objective}
         return eng.mc_acq(self.kind, mean, var, self._z, self.best_f, self.sign, self.beta, alive=alive, **okw)
 
-    def greedy(self, Xd, batch_size: int, seed: int, X_pending=None, alive=None, **_unused) -> GreedyResult:
+    def greedy(self, Xd, batch_size: int, seed: int, X_pending=None, alive=None) -> GreedyResult:
         if batch_size != 1:
-            raise IncompatibleSurrogateError(f"'{type(self.outputs[0]).__name__}' {JOINT_TEXT}.")
+            raise IncompatibleSurrogateError(f"'{self.name}' {JOINT_TEXT}.")
         self.prepare(seed, X_pending)
         val, idx = self.engine.argmax(self.score(Xd, alive))
         return GreedyResult([int(idx)], [float(val)])
+
+    # ---- the recommender's surface (``baybe_amd.scoring``): ONE sampler seed per call ----------------------------------------------
+    supports_continuous = False
+
+    @staticmethod
+    def check_request(batch_size, n_pend, acqf=None, program=None, model=None) -> None:
+        refuse_joint(type(model).__name__, batch_size, n_pend)
+
+    def select(self, X, q, *, seeds, X_pending=None, alive=None, shard=None) -> GreedyResult:
+        refuse_shard(shard, shard_text(self.name))
+        return self.greedy(X, q, seeds(), X_pending, alive)
+
+    def values(self, X, *, seeds, X_pending=None):
+        self.prepare(seeds(), X_pending)
+        return self.score(self.engine._as_dev(X))
+
+    def joint_value(self, batch, *, seeds, X_pending=None) -> float:
+        refuse_joint(self.name, len(batch), 0)
+        return float(self.values(batch, seeds=seeds, X_pending=X_pending).cpu().numpy()[0])
+
+
+class HipLinearAnalytic(HipSingleTargetAcq):
+    """The analytic acquisition functions on the linear model's moments: ``HipSingleTargetAcq`` under the one-point rule."""
+
+    supports_continuous = False
+    check_request = staticmethod(HipLinearAcq.check_request)
+
+    def __init__(self, surrogate, acqf, sign: float, best_f: float, program=None):
+        super().__init__(surrogate.engine, acqf, sign, best_f, program)
+        self.name = type(surrogate).__name__
+
+    def joint_value(self, batch, *, seeds, X_pending=None) -> float:
+        refuse_joint(self.name, len(batch), 0)
+        return super().joint_value(batch, seeds=seeds, X_pending=X_pending)
 
 
 # ---- the surrogate -----------------------------------------------------------------------------------------------------------------------

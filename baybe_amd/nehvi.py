@@ -43,6 +43,7 @@ import numpy as np
 from baybe_amd import _lib
 from baybe_amd.box_decomposition import pack_cells_native, pareto_mask
 from baybe_amd.engine import GreedyResult, HipGP, _dp, _native_sobol_usable, draw_sampler_seed, sobol_normal_base_samples
+from baybe_amd.scoring import no_batch_cap
 
 PRUNE_SAMPLES = 2048  # prune_inferior_points_multi_objective(num_samples=2048)
 
@@ -456,6 +457,30 @@ class HipNEHVI:
             values.append(float(val))
             picks.append(np.asarray(row, dtype=np.float64).reshape(1, d))
         return GreedyResult(indices, values)
+
+    # ---- the recommender's surface (``baybe_amd.scoring``); shared by the subclasses and their CPU doubles -------------------
+    supports_continuous = False
+    check_request = staticmethod(no_batch_cap)
+
+    def select(self, X, q, *, seeds, X_pending=None, alive=None, shard=None) -> GreedyResult:
+        """The scoring seed, then the pruning seed (drawn whether or not anything is pruned)."""
+        return self.greedy(X, q, seed=seeds(), prune_seed=seeds(), X_pending=X_pending, alive=alive, shard=shard)
+
+    def _prepare_drawing(self, seeds, extra_baseline):
+        """``prepare`` for a read-back: the scoring seed, then - only where this call prunes - a local pruning seed."""
+        seed = seeds()
+        pruning = self._pruned is None and self.prune and len(self.X_baseline)
+        self.prepare(seed, extra_baseline, seeds(agree=False) if pruning else None)
+
+    def values(self, X, *, seeds, X_pending=None):
+        self._prepare_drawing(seeds, X_pending)
+        return self.score(self.outputs[0].engine._as_dev(X))
+
+    def joint_value(self, batch, *, seeds, X_pending=None) -> float:
+        """Incremental: the batch value is the value of its last point given the others (and the pending rows) in the baseline."""
+        rest = [batch[:-1]] + ([X_pending] if X_pending is not None else [])
+        self._prepare_drawing(seeds, np.vstack(rest) if len(batch) > 1 or X_pending is not None else None)
+        return float(self.score(self.outputs[0].engine._as_dev(batch[-1:])).cpu().numpy()[0])
 
 
 class HipNEHVIPlain(HipNEHVI):

@@ -28,6 +28,7 @@ import pandas as pd
 
 from baybe_amd.engine import GreedyResult, draw_sampler_seed
 from baybe_amd.exceptions import IncompatibilityError
+from baybe_amd.scoring import refuse_shard
 
 MAX_TRAINING_POINTS = 512  # csrc/bbh_nipv.hip
 NIPV_KERNELS = ("matern12", "matern32", "matern52", "rbf")
@@ -60,6 +61,9 @@ def integration_points(acqf, searchspace, device: int = 0) -> pd.DataFrame:
     method = str(getattr(acqf.sampling_method, "value", acqf.sampling_method))
     values = comp.values if method == "FPS" else None
     return comp.iloc[integration_ilocs(len(comp), n, method, values, device)]
+
+
+SHARD_TEXT = "Row shards are not on the HIP path of qNIPV; score the candidates on one device."
 
 
 def check_batch(n_points: int) -> None:
@@ -145,9 +149,25 @@ class HipNIPV:
         g, v_b = self.gain(X, X_pending, alive)
         return g / self.M - v_b
 
-    def joint_value(self, batch, X_pending=None, seed=None) -> float:
+    # ---- the recommender's surface (``baybe_amd.scoring``): one seed per call, drawn and unused ---------------------------------
+    supports_continuous = False
+
+    @staticmethod
+    def check_request(batch_size, n_pend, acqf=None, program=None, model=None) -> None:
+        """The model is conditioned on the pending experiments and the picks through the handle's pending state."""
+        check_batch(n_pend + batch_size)
+
+    def select(self, X, q, *, seeds, X_pending=None, alive=None, shard=None) -> GreedyResult:
+        refuse_shard(shard, SHARD_TEXT)
+        return self.greedy(X, q, seed=seeds(), X_pending=X_pending, alive=alive)
+
+    def values(self, X, *, seeds, X_pending=None):
+        return self.score(X, X_pending=X_pending, seed=seeds())
+
+    def joint_value(self, batch, *, seeds, X_pending=None) -> float:
         """The value of the whole batch ``[batch ; X_pending]``: its first point scored with the others pending (the value is
         symmetric in the points)."""
+        seeds()
         batch = np.atleast_2d(np.asarray(batch, dtype=np.float64))
         rest = np.vstack([self._pend(batch[1:]), self._pend(X_pending)])
         return float(self.score(batch[:1], X_pending=rest).cpu().numpy()[0])

@@ -298,6 +298,33 @@ def _gradient_kernel_refusal(surrogate, searchspace):
     return None
 
 
+def _choose_scorer(model, acqf, program):
+    """(path, scorer class) serving a surrogate model, an acquisition function and an objective program - the one place a path is
+    chosen: ``_setup_acqf`` builds that scorer, ``_check_batch_size`` asks the class for its cap before anything is fitted.  The
+    objective enters through what ``_check_objective`` made of it: ``program``, and a multi-output objective exactly where the
+    acquisition function is a multi-output one.  Classes are looked up per call, so that the tests' CPU doubles are found."""
+    from baybe_amd import desirability, ehvi, forest, linear, nehvi, nei, nipv, nparego, scoring
+
+    kind, analytic = getattr(acqf, "kind", None), getattr(acqf, "is_analytic", False)
+    if getattr(model, "is_independent_gaussian", False):
+        return ("linear_analytic", linear.HipLinearAnalytic) if analytic else ("linear", linear.HipLinearAcq)
+    if _is_ehvi(acqf):
+        return "ehvi", ehvi.HipEHVI
+    if _is_nipv(acqf):
+        return "nipv", nipv.HipNIPV
+    if _is_desirability(program):
+        return "desirability", desirability.HipDesirability
+    if kind == "qLogNParEGO":
+        return "nparego", nparego.HipNParEGO
+    if getattr(acqf, "supports_multi_output", False):
+        return "nehvi", nehvi.HipNEHVIPlain if kind == "qNEHVI" else nehvi.HipNEHVI
+    if kind in ("qNEI", "qLogNEI"):
+        return "nei", nei.HipNEI
+    if getattr(model, "is_ensemble", False) and not analytic:
+        return "forest", forest.HipForestAcq
+    return "single", scoring.HipSingleTargetAcq  # (and the analytic kinds on the forest's ensemble moments)
+
+
 class HipRecommenderImpl:
     """Behaviour of the Bayesian recommender scoring the full discrete candidate set on an MI355X.  No fields: they
     are attached by ``attrs.make_class`` - below for the stand-alone class, in ``baybe_amd.plugin`` on top of BayBE's
@@ -311,7 +338,7 @@ class HipRecommenderImpl:
 
     # ---- copies (simulation/core.py:124, scenarios.py:296, transfer_learning.py:78 deep-copy whole campaigns) --------
     _SHARED_ON_COPY: ClassVar[tuple] = ("_cand_cache", "shard")  # resident candidate matrix (up to 160 MB of HBM): shared, read-only
-    _DROPPED_ON_COPY: ClassVar[tuple] = ("_nehvi",)  # per-call acquisition state holding device handles: rebuilt by every recommend()
+    _DROPPED_ON_COPY: ClassVar[tuple] = ("_scorer",)  # per-call acquisition state holding device handles: rebuilt by every recommend()
 
     def __deepcopy__(self, memo):
         from copy import deepcopy
@@ -370,46 +397,21 @@ class HipRecommenderImpl:
         self._setup_acqf(searchspace, objective, measurements, pending_experiments)
 
     def _setup_acqf(self, searchspace, objective, measurements, pending_experiments=None, acquisition_function=None):
-        """Native counterpart of ``_setup_botorch_acqf``: fit (cached), best_f, pending rows."""
+        """Native counterpart of ``_setup_botorch_acqf``: the refusals of the surrogate's path (before anything is fitted), the fit
+        (cached), the pending rows, and the path's scorer (``baybe_amd.scoring``) with its incumbent."""
         cont = getattr(searchspace, "continuous", None)
-        if _is_nipv(self._get_acquisition_function(objective, acquisition_function)):  # (before anything is fitted, whatever the surrogate)
+        acqf = self._get_acquisition_function(objective, acquisition_function)
+        if _is_nipv(acqf):  # (before anything is fitted, whatever the surrogate)
             self._check_nipv_context(searchspace, objective, measurements)
         if self.continuous_optimizer == "gradient" and cont is not None and not getattr(cont, "is_empty", True):
             self._check_gradient_context(searchspace, objective, measurements, acquisition_function)
-        if getattr(self._surrogate_model, "is_ensemble", False):
-            return self._setup_forest_acqf(searchspace, objective, measurements, pending_experiments, acquisition_function)
-        if getattr(self._surrogate_model, "is_independent_gaussian", False):
-            return self._setup_linear_acqf(searchspace, objective, measurements, pending_experiments, acquisition_function)
-        if cont is not None and not getattr(cont, "is_empty", True):
-            _check_continuous_part(cont, self.continuous_optimizer)  # hybrid / continuous spaces: box-bounded continuous parameters only
         self._objective = objective
-        acqf = self._get_acquisition_function(objective, acquisition_function)
-        self._program = _check_objective(objective, acqf, self.desirability)
-        if _is_desirability(self._program):  # (before anything is fitted)
-            if cont is not None and not getattr(cont, "is_empty", True):
-                raise IncompatibilityError(
-                    "Desirability objectives with one model per target are scored over discrete search spaces on the HIP path, not "
-                    "hybrid / continuous ones; use 'DesirabilityObjective(as_pre_transformation=True)' or BotorchRecommender.")
-            if self.shard is not None:
-                raise IncompatibilityError(
-                    "Row shards are not on the HIP path of desirability objectives with one model per target; score them on one "
-                    "device, or use 'DesirabilityObjective(as_pre_transformation=True)'.")
-        if _is_ehvi(acqf):  # (before anything is fitted)
-            from baybe_amd.ehvi import MAX_OBJECTIVES, check_alpha
-
-            check_alpha(acqf.alpha)
-            if len(objective.targets) > MAX_OBJECTIVES:
-                raise IncompatibilityError(
-                    f"'{type(acqf).__name__}' is scored for 2 to {MAX_OBJECTIVES} targets on the HIP path "
-                    f"({len(objective.targets)} given). Use BotorchRecommender.")
-            if cont is not None and not getattr(cont, "is_empty", True):
-                raise IncompatibilityError(
-                    f"'{type(acqf).__name__}' is scored over discrete search spaces on the HIP path, not hybrid / continuous ones; "
-                    f"use BotorchRecommender.")
-            if self.shard is not None:
-                raise IncompatibilityError(
-                    f"Row shards are not on the HIP path of '{type(acqf).__name__}'; score the candidates on one device, or use "
-                    f"qLogNoisyExpectedHypervolumeImprovement.")
+        if getattr(self._surrogate_model, "is_ensemble", False):
+            self._refuse_for_forest(searchspace, objective, acqf)
+        elif getattr(self._surrogate_model, "is_independent_gaussian", False):
+            self._refuse_for_linear(searchspace, objective, acqf, pending_experiments)
+        else:
+            self._refuse_for_gp(searchspace, objective, acqf)
         self._acqf_in_use = acqf
         if pending_experiments is not None and not acqf.supports_pending_experiments:
             raise IncompatibleAcquisitionFunctionError(
@@ -420,79 +422,153 @@ class HipRecommenderImpl:
         if pending_experiments is not None and len(pending_experiments):
             pend = searchspace.transform(pending_experiments, allow_extra=True)  # _builder.py:326-334
             self._pending_comp = np.ascontiguousarray(pend.to_numpy(dtype=np.float64))
-        self._nehvi = None
-        if _is_desirability(self._program):
-            from baybe_amd.desirability import HipDesirability
+        self._scorer, self._best_f = self._build_scorer(surrogate, searchspace, objective, measurements, acqf)
+        return surrogate, acqf
 
-            # the incumbent is the desirability of the models' means at ALL measurement rows (_builder.py:141-161, 256-265)
-            X_all = np.ascontiguousarray(searchspace.transform(measurements, allow_extra=True).to_numpy(dtype=np.float64))
+    def _refuse_for_gp(self, searchspace, objective, acqf) -> None:
+        """What the Gaussian process paths do not cover, before anything is fitted; sets the objective program."""
+        cont = getattr(searchspace, "continuous", None)
+        hybrid = cont is not None and not getattr(cont, "is_empty", True)
+        if hybrid:
+            _check_continuous_part(cont, self.continuous_optimizer)  # hybrid / continuous spaces: box-bounded continuous parameters only
+        self._program = _check_objective(objective, acqf, self.desirability)
+        if _is_desirability(self._program):
+            from baybe_amd.desirability import SHARD_TEXT
+
+            if hybrid:
+                raise IncompatibilityError(
+                    "Desirability objectives with one model per target are scored over discrete search spaces on the HIP path, not "
+                    "hybrid / continuous ones; use 'DesirabilityObjective(as_pre_transformation=True)' or BotorchRecommender.")
+            if self.shard is not None:
+                raise IncompatibilityError(SHARD_TEXT)
+        if _is_ehvi(acqf):
+            from baybe_amd.ehvi import MAX_OBJECTIVES, check_alpha, shard_text
+
+            check_alpha(acqf.alpha)
+            if len(objective.targets) > MAX_OBJECTIVES:
+                raise IncompatibilityError(
+                    f"'{type(acqf).__name__}' is scored for 2 to {MAX_OBJECTIVES} targets on the HIP path "
+                    f"({len(objective.targets)} given). Use BotorchRecommender.")
+            if hybrid:
+                raise IncompatibilityError(
+                    f"'{type(acqf).__name__}' is scored over discrete search spaces on the HIP path, not hybrid / continuous ones; "
+                    f"use BotorchRecommender.")
+            if self.shard is not None:
+                raise IncompatibilityError(shard_text(type(acqf).__name__))
+
+    def _refuse_beyond_single_output(self, objective, acqf, posterior: str) -> None:
+        """The forest and linear surrogates model one target and have no noisy / multi-output acquisition functions."""
+        from baybe_amd.exceptions import IncompatibleSurrogateError
+        from baybe_amd.surrogates import modeled_quantities
+
+        name = type(self._surrogate_model).__name__
+        if _is_multi_output(objective) or len(modeled_quantities(objective)) > 1:
+            raise IncompatibleSurrogateError(
+                f"'{name}' is a single-output surrogate; multi-target objectives are not on its HIP path. Use BotorchRecommender."
+            )
+        if acqf.supports_multi_output or getattr(acqf, "kind", None) in ("qNEI", "qLogNEI"):
+            raise IncompatibleAcquisitionFunctionError(
+                f"The acquisition function '{type(acqf).__name__}' is not on the HIP path of '{name}': its {posterior} "
+                f"posterior is scored by qLogEI, qEI, qPI, qSR, qUCB, qPSTD and the analytic acquisition functions."
+            )
+
+    def _refuse_for_forest(self, searchspace, objective, acqf) -> None:
+        """What the path of an ensemble surrogate (``baybe_amd.forest.HipRandomForestSurrogate``) does not cover, before anything
+        is fitted."""
+        from baybe_amd.forest import refuse_continuous, shard_text
+
+        refuse_continuous(searchspace)
+        name = type(self._surrogate_model).__name__
+        if self.shard is not None:
+            raise IncompatibilityError(shard_text(name))
+        self._refuse_beyond_single_output(objective, acqf, "ensemble")
+        self._program = _check_objective(objective, acqf)
+        if self._program is not None:
+            raise IncompatibilityError(
+                f"Target '{objective.targets[0].name}' carries a transformation; the HIP path of '{name}' supports identity "
+                f"transformations with optional minimisation only."
+            )
+
+    def _refuse_for_linear(self, searchspace, objective, acqf, pending_experiments) -> None:
+        """What the path of an independent-Gaussian surrogate (``baybe_amd.linear.HipBayesianLinearSurrogate``) does not cover,
+        before anything is fitted.  A transformed single target rides on the objective program, as on the GP path."""
+        from baybe_amd.forest import refuse_continuous
+        from baybe_amd.linear import refuse_joint, refuse_task_parameters, shard_text
+
+        name = type(self._surrogate_model).__name__
+        refuse_task_parameters(searchspace, name)
+        refuse_continuous(searchspace)
+        self._refuse_beyond_single_output(objective, acqf, "independent Gaussian")
+        refuse_joint(name, 1, 0 if pending_experiments is None else len(pending_experiments))
+        if self.shard is not None:
+            raise IncompatibilityError(shard_text(name))
+        self._program = _check_objective(objective, acqf)
+
+    def _build_scorer(self, surrogate, searchspace, objective, measurements, acqf):
+        """(scorer, best_f) of the chosen path: its incumbent and its constructor arguments."""
+        path, cls = _choose_scorer(self._surrogate_model, acqf, self._program)
+        program, beta = self._program, getattr(acqf, "beta", 0.2)
+
+        def measured_rows():  # ALL measurement rows: the noisy forms' baseline (_builder.py:319-324), the incumbent's rows (141-161, 256-265)
+            return np.ascontiguousarray(searchspace.transform(measurements, allow_extra=True).to_numpy(dtype=np.float64))
+
+        if path == "desirability":
             engines = [m.engine for m in surrogate.models]
-            scorer = HipDesirability(engines, self._program, X_all, acqf.kind, getattr(acqf, "n_mc_samples", 512),
-                                     getattr(acqf, "beta", 0.2), device=engines[0].device)
-            self._best_f = scorer.best_f()
-            if not acqf.is_analytic:  # (analytic functions read the combined Gaussian moments: ``_desirability_moments``)
-                self._nehvi = scorer
-        elif _is_multi_output(objective):
+            scorer = cls(engines, program, measured_rows(), acqf.kind, getattr(acqf, "n_mc_samples", 512), beta,
+                         device=engines[0].device, analytic=acqf.is_analytic, maximize=getattr(acqf, "maximize", True))
+            return scorer, scorer.best_f()  # the desirability of the models' means at all measurement rows
+        if path in ("nparego", "nehvi", "ehvi"):
             models = surrogate.models
-            signs = np.array([m.sign for m in models])
-            X_base = np.ascontiguousarray(searchspace.transform(measurements, allow_extra=True).to_numpy(dtype=np.float64))
-            if acqf.kind == "qLogNParEGO":
-                from baybe_amd.nparego import HipNParEGO, draw_scalarization_weights
+            engines, signs, X_base = [m.engine for m in models], np.array([m.sign for m in models]), measured_rows()
+            if path == "nparego":
+                from baybe_amd.nparego import draw_scalarization_weights
 
                 # the weights are fixed when the acquisition function is built: before the scoring and pruning seeds are drawn
                 weights = acqf.scalarization_weights
                 if weights is None:
                     weights = draw_scalarization_weights(len(models), self.shard.agree if self.shard is not None else None)
-                self._nehvi = HipNParEGO([m.engine for m in models], signs, X_base, weights, n_mc_samples=acqf.n_mc_samples,
-                                         prune_baseline=acqf.prune_baseline, device=models[0].engine.device)
-            else:  # the hypervolume kinds
-                from baybe_amd.nehvi import HipNEHVI, HipNEHVIPlain, compute_ref_point
-
-                names = [t.name for t in objective.targets]
-                ref = acqf.reference_point
-                if not isinstance(ref, tuple):  # _builder.py:301-317: from completely measured rows
-                    complete = measurements[names].dropna()
-                    if complete.empty:
-                        raise ValueError(
-                            "For calculating a default reference point, at least one configuration must have a "
-                            "measured value for all targets. Set 'reference_point' explicitly."
-                        )
-                    kw = {} if ref is None else {"factor": ref}
-                    ref = compute_ref_point(complete.to_numpy(dtype=np.float64) * signs[None, :], **kw)
-                if _is_ehvi(acqf):
-                    from baybe_amd.ehvi import HipEHVI
-
-                    # the partitioning comes from the models' posterior means at ALL measurement rows (_builder.py:286-299)
-                    self._nehvi = HipEHVI([m.engine for m in models], signs, X_base, np.asarray(ref, dtype=np.float64),
-                                          log=acqf.kind == "qLogEHVI", n_mc_samples=acqf.n_mc_samples, alpha=acqf.alpha,
-                                          device=models[0].engine.device)
-                    self._best_f = None
-                    return surrogate, acqf
-                scorer = HipNEHVIPlain if acqf.kind == "qNEHVI" else HipNEHVI
-                self._nehvi = scorer([m.engine for m in models], signs, X_base, np.asarray(ref, dtype=np.float64),
-                                     n_mc_samples=acqf.n_mc_samples, prune_baseline=acqf.prune_baseline,
-                                     device=models[0].engine.device)
-            self._best_f = None
-        elif acqf.kind in ("qNEI", "qLogNEI"):
-            from baybe_amd.nei import HipNEI
-
-            # the noisy forms have no incumbent value: the baseline (all training inputs, _builder.py:319-324) is sampled instead
-            X_base = np.ascontiguousarray(searchspace.transform(measurements, allow_extra=True).to_numpy(dtype=np.float64))
-            self._nehvi = HipNEI(surrogate.engine, self._sign(surrogate), X_base, n_mc_samples=acqf.n_mc_samples,
-                                 prune_baseline=acqf.prune_baseline, log=acqf.kind == "qLogNEI", device=surrogate.engine.device)
-            self._best_f = None
-        elif _is_nipv(acqf):
-            from baybe_amd.nipv import HipNIPV, integration_points
+                return cls(engines, signs, X_base, weights, n_mc_samples=acqf.n_mc_samples, prune_baseline=acqf.prune_baseline,
+                           device=engines[0].device), None
+            ref = np.asarray(self._ref_point(acqf, objective, measurements, signs), dtype=np.float64)
+            if path == "ehvi":  # the partitioning comes from the models' posterior means at ALL measurement rows (_builder.py:286-299)
+                return cls(engines, signs, X_base, ref, log=acqf.kind == "qLogEHVI", n_mc_samples=acqf.n_mc_samples,
+                           alpha=acqf.alpha, device=engines[0].device), None
+            return cls(engines, signs, X_base, ref, n_mc_samples=acqf.n_mc_samples, prune_baseline=acqf.prune_baseline,
+                       device=engines[0].device), None
+        eng = surrogate.engine
+        sign = 1.0 if program is not None else surrogate.sign  # the kernels' ``sign``: +1 where an objective program carries the orientation
+        if path == "nei":  # no incumbent value: the baseline is sampled instead
+            return cls(eng, sign, measured_rows(), n_mc_samples=acqf.n_mc_samples, prune_baseline=acqf.prune_baseline,
+                       log=acqf.kind == "qLogNEI", device=eng.device), None
+        if path == "nipv":
+            from baybe_amd.nipv import integration_points
 
             # the integration points are sampled from ALL rows of the discrete subspace when the acquisition function is built
-            P = integration_points(acqf, searchspace, device=surrogate.engine.device)
-            self._nehvi = HipNIPV(surrogate.engine, P.to_numpy(dtype=np.float64), device=surrogate.engine.device)
-            self._best_f = None
-        else:
-            # _builder.py:141-161, 256-265: the transformed posterior mean at the training inputs
-            eng = surrogate.engine
-            self._best_f = eng.best_f(surrogate.sign) if self._program is None else eng.best_f(1.0, self._program)
-        return surrogate, acqf
+            P = integration_points(acqf, searchspace, device=eng.device)
+            return cls(eng, P.to_numpy(dtype=np.float64), device=eng.device), None
+        # _builder.py:141-161, 256-265: the transformed posterior mean at the training inputs
+        best_f = eng.best_f(surrogate.sign) if program is None else eng.best_f(1.0, program)
+        if path == "forest":
+            return cls(surrogate, acqf.kind, sign, best_f, acqf.n_mc_samples, beta), best_f
+        if path == "linear":
+            return cls(surrogate, acqf.kind, sign, best_f, acqf.n_mc_samples, beta, program), best_f
+        return cls(surrogate if path == "linear_analytic" else eng, acqf, sign, best_f, program), best_f
+
+    @staticmethod
+    def _ref_point(acqf, objective, measurements, signs):
+        ref = acqf.reference_point
+        if isinstance(ref, tuple):
+            return ref
+        from baybe_amd.nehvi import compute_ref_point
+
+        complete = measurements[[t.name for t in objective.targets]].dropna()  # _builder.py:301-317: from completely measured rows
+        if complete.empty:
+            raise ValueError(
+                "For calculating a default reference point, at least one configuration must have a "
+                "measured value for all targets. Set 'reference_point' explicitly."
+            )
+        kw = {} if ref is None else {"factor": ref}
+        return compute_ref_point(complete.to_numpy(dtype=np.float64) * signs[None, :], **kw)
 
     def _check_nipv_context(self, searchspace, objective, measurements) -> None:
         """What qNIPV covers on the device - one untransformed target, a discrete space, a single-task GP with one Matern / RBF
@@ -555,130 +631,13 @@ class HipRecommenderImpl:
         if self.shard is not None and getattr(self.shard, "world", 1) > 1:
             raise IncompatibilityError(f"continuous_optimizer='gradient' runs on one device, not under row shards; {use}.")
 
-    def _setup_forest_acqf(self, searchspace, objective, measurements, pending_experiments=None, acquisition_function=None):
-        """``_setup_acqf`` for an ensemble surrogate (``baybe_amd.forest.HipRandomForestSurrogate``): what the forest path does not
-        cover is refused before anything is fitted; then the fit (cached), best_f = max_i sign * mean_t P_t(x_i) over the training
-        inputs (_builder.py:141-161), the pending rows, and - for the MC acquisition functions - the forest scorer in the slot of the
-        other device scorers.  Analytic acquisition functions need nothing more: they read the ensemble moments."""
-        from baybe_amd.exceptions import IncompatibleSurrogateError
-        from baybe_amd.forest import HipForestAcq, refuse_continuous
-        from baybe_amd.surrogates import modeled_quantities
-
-        refuse_continuous(searchspace)
-        name = type(self._surrogate_model).__name__
-        if self.shard is not None:
-            raise IncompatibilityError(f"Row shards are not on the HIP path of '{name}'; score the forest on one device.")
-        self._objective = objective
-        acqf = self._get_acquisition_function(objective, acquisition_function)
-        if _is_multi_output(objective) or len(modeled_quantities(objective)) > 1:
-            raise IncompatibleSurrogateError(
-                f"'{name}' is a single-output surrogate; multi-target objectives are not on its HIP path. Use BotorchRecommender."
-            )
-        if acqf.supports_multi_output or getattr(acqf, "kind", None) in ("qNEI", "qLogNEI"):
-            raise IncompatibleAcquisitionFunctionError(
-                f"The acquisition function '{type(acqf).__name__}' is not on the HIP path of '{name}': its ensemble posterior is "
-                f"scored by qLogEI, qEI, qPI, qSR, qUCB, qPSTD and the analytic acquisition functions."
-            )
-        self._program = _check_objective(objective, acqf)
-        if self._program is not None:
-            raise IncompatibilityError(
-                f"Target '{objective.targets[0].name}' carries a transformation; the HIP path of '{name}' supports identity "
-                f"transformations with optional minimisation only."
-            )
-        self._acqf_in_use = acqf
-        if pending_experiments is not None and not acqf.supports_pending_experiments:
-            raise IncompatibleAcquisitionFunctionError(
-                f"The chosen acquisition function of type '{type(acqf).__name__}' does not support pending experiments."
-            )
-        surrogate = self.get_surrogate(searchspace, objective, measurements)
-        self._pending_comp = None
-        if pending_experiments is not None and len(pending_experiments):
-            pend = searchspace.transform(pending_experiments, allow_extra=True)  # _builder.py:326-334
-            self._pending_comp = np.ascontiguousarray(pend.to_numpy(dtype=np.float64))
-        self._best_f = surrogate.engine.best_f(surrogate.sign)
-        self._nehvi = None
-        if not acqf.is_analytic:
-            self._nehvi = HipForestAcq(surrogate, acqf.kind, surrogate.sign, self._best_f, acqf.n_mc_samples, getattr(acqf, "beta", 0.2))
-        return surrogate, acqf
-
-    def _setup_linear_acqf(self, searchspace, objective, measurements, pending_experiments=None, acquisition_function=None):
-        """``_setup_acqf`` for an independent-Gaussian surrogate (``baybe_amd.linear.HipBayesianLinearSurrogate``): what its path does
-        not cover is refused before anything is fitted; then the fit (cached), best_f = max_i objective(mean at training row i)
-        (_builder.py:141-161), and - for the MC acquisition functions - the q = 1 scorer in the slot of the other device scorers.
-        Analytic acquisition functions need nothing more: they read the moments.  A transformed single target rides on the objective
-        program, as on the GP path."""
-        from baybe_amd.exceptions import IncompatibleSurrogateError
-        from baybe_amd.forest import refuse_continuous
-        from baybe_amd.linear import JOINT_TEXT, HipLinearAcq, refuse_task_parameters
-        from baybe_amd.surrogates import modeled_quantities
-
-        name = type(self._surrogate_model).__name__
-        refuse_task_parameters(searchspace, name)
-        refuse_continuous(searchspace)
-        self._objective = objective
-        acqf = self._get_acquisition_function(objective, acquisition_function)
-        if _is_multi_output(objective) or len(modeled_quantities(objective)) > 1:
-            raise IncompatibleSurrogateError(
-                f"'{name}' is a single-output surrogate; multi-target objectives are not on its HIP path. Use BotorchRecommender."
-            )
-        if acqf.supports_multi_output or getattr(acqf, "kind", None) in ("qNEI", "qLogNEI"):
-            raise IncompatibleAcquisitionFunctionError(
-                f"The acquisition function '{type(acqf).__name__}' is not on the HIP path of '{name}': its independent Gaussian "
-                f"posterior is scored by qLogEI, qEI, qPI, qSR, qUCB, qPSTD and the analytic acquisition functions."
-            )
-        if pending_experiments is not None and len(pending_experiments):
-            raise IncompatibleSurrogateError(f"'{name}' {JOINT_TEXT}.")
-        if self.shard is not None:
-            raise IncompatibilityError(f"Row shards are not on the HIP path of '{name}'; score the linear model on one device.")
-        self._program = _check_objective(objective, acqf)
-        self._acqf_in_use = acqf
-        surrogate = self.get_surrogate(searchspace, objective, measurements)
-        self._pending_comp = None
-        eng = surrogate.engine
-        self._best_f = eng.best_f(surrogate.sign) if self._program is None else eng.best_f(1.0, self._program)
-        self._nehvi = None
-        if not acqf.is_analytic:
-            self._nehvi = HipLinearAcq(surrogate, acqf.kind, self._sign(surrogate), self._best_f, acqf.n_mc_samples,
-                                       getattr(acqf, "beta", 0.2), self._program)
-        return surrogate, acqf
-
     def _check_batch_size(self, batch_size, pending_experiments=None) -> None:
-        """The joint q'-batch kernels hold 1 + (pending + earlier picks) <= 16 points; the reference has no such
-        limit, so say so before any candidate is scored (single-target MC acquisition functions only: qLogNEHVI and
-        qNEI / qLogNEI cache picks into their baseline and analytic functions have q = 1)."""
+        """The cap of the chosen path (``check_request``, beside its scorer): the reference has no such limit, so say so before
+        any candidate is scored - and, from ``recommend``, before the fit."""
         n_pend = len(self._pending_comp) if self._pending_comp is not None else (
             0 if pending_experiments is None else len(pending_experiments))
-        if getattr(self._surrogate_model, "is_independent_gaussian", False):
-            # an independent Gaussian per point has no joint posterior (surrogates/base.py:484-503): one point, nothing pending
-            if batch_size > 1 or n_pend > 0:
-                from baybe_amd.exceptions import IncompatibleSurrogateError
-                from baybe_amd.linear import JOINT_TEXT
-
-                raise IncompatibleSurrogateError(f"'{type(self._surrogate_model).__name__}' {JOINT_TEXT}.")
-            return
-        acqf = self._acqf_in_use
-        if _is_ehvi(acqf):  # the candidate, the pending experiments and the picks are ONE joint batch (no baseline to cache them into)
-            from baybe_amd.ehvi import HipEHVI
-
-            HipEHVI.check_batch(1 + n_pend + batch_size)
-            return
-        if _is_nipv(acqf):  # the model is conditioned on the pending experiments and the picks through the handle's pending state
-            from baybe_amd.nipv import check_batch
-
-            check_batch(n_pend + batch_size)
-            return
-        if acqf is not None and (acqf.supports_multi_output or getattr(acqf, "is_analytic", False)
-                                 or getattr(acqf, "kind", None) in ("qNEI", "qLogNEI")):
-            return
-        # qLogEI: up to 64 points (beyond 16 through bbh_qlogei_pending_big, the factor in a global workspace); the other MC
-        # acquisition functions, and every one under an objective program (bbh_mc_acq_obj_pending): 16
-        big = getattr(acqf, "kind", None) == "qLogEI" and self._program is None
-        cap = (_lib.MAX_PENDING_BIG if big else _lib.MAX_PENDING) + 1
-        if batch_size + n_pend > cap:
-            raise IncompatibilityError(
-                f"batch_size ({batch_size}) + pending experiments ({n_pend}) exceeds {cap}, the largest "
-                f"joint q-batch of the HIP kernels; recommend in smaller batches (marking earlier ones as pending)."
-            )
+        _, cls = _choose_scorer(self._surrogate_model, self._acqf_in_use, self._program)
+        cls.check_request(batch_size, n_pend, self._acqf_in_use, self._program, self._surrogate_model)
 
     def recommend(self, batch_size, searchspace, objective=None, measurements=None, pending_experiments=None) -> pd.DataFrame:
         if objective is None:
@@ -726,10 +685,11 @@ class HipRecommenderImpl:
         return searchspace.discrete.exp_rep.loc[idxs, :]
 
     # ---- discrete optimisation -----------------------------------------------------------------
-    def _sampler_seed(self) -> int:
-        """MC sampler seed from torch's global RNG (``engine.draw_sampler_seed``); with row shards rank 0's draw."""
+    def _sampler_seed(self, agree: bool = True) -> int:
+        """MC sampler seed from torch's global RNG (``engine.draw_sampler_seed``); with row shards rank 0's draw.  The scorers'
+        ``seeds`` (``baybe_amd.scoring``); ``agree=False``: this rank's own draw."""
         seed = draw_sampler_seed()
-        return int(self.shard.agree(seed)) if self.shard is not None else seed
+        return int(self.shard.agree(seed)) if agree and self.shard is not None else seed
 
     def _candidates_on_device(self, subspace_discrete, candidates_exp, keep_mask=None):
         """(X_dev, alive, labels): the *whole* comp rep of the discrete subspace as a device-resident
@@ -779,10 +739,6 @@ class HipRecommenderImpl:
             alive = torch.from_numpy(mask).to(Xd.device)
         return Xd, alive, labels
 
-    def _sign(self, surrogate) -> float:
-        """The ``sign`` argument of the kernels: the target's orientation, or +1 where an objective program carries it."""
-        return 1.0 if self._program is not None else surrogate.sign
-
     @property
     def _engine(self):
         model = self._surrogate_model
@@ -802,43 +758,9 @@ class HipRecommenderImpl:
 
     def _recommend_discrete_without_subsets(self, subspace_discrete, candidates_exp, batch_size, return_values=False,
                                             keep_mask=None):
-        surrogate = self._surrogate_model
-        acqf = self._acqf_in_use
         Xd, alive, labels = self._candidates_on_device(subspace_discrete, candidates_exp, keep_mask)
-        if self._nehvi is not None and (_is_desirability(self._program) or _is_ehvi(self._acqf_in_use) or _is_nipv(self._acqf_in_use)):
-            # the desirability / hypervolume-improvement scorers: ONE sampler seed per recommendation, as on the single-target path
-            res = self._nehvi.greedy(Xd, batch_size, seed=self._sampler_seed(), X_pending=self._pending_comp, alive=alive)
-            idxs = labels[np.asarray(res.indices, dtype=np.int64)]
-            return (idxs, res) if return_values else idxs
-        if self._nehvi is not None and (getattr(surrogate, "is_ensemble", False) or getattr(surrogate, "is_independent_gaussian", False)):
-            # the forest / linear scorer: ONE sampler seed per recommendation (their posteriors have no pruning draw)
-            res = self._nehvi.greedy(Xd, batch_size, seed=self._sampler_seed(), X_pending=self._pending_comp, alive=alive)
-            idxs = labels[np.asarray(res.indices, dtype=np.int64)]
-            return (idxs, res) if return_values else idxs
-        if self._nehvi is not None:
-            res = self._nehvi.greedy(Xd, batch_size, seed=self._sampler_seed(), prune_seed=self._sampler_seed(),
-                                     X_pending=self._pending_comp, alive=alive, shard=self.shard)
-            idxs = labels[np.asarray(res.indices, dtype=np.int64)]
-            return (idxs, res) if return_values else idxs
-        if acqf.is_analytic:  # q = 1 by construction (supports_batching is False)
-            if _is_desirability(self._program):
-                eng, mean, var = self._desirability_moments(Xd)
-            else:
-                eng = surrogate.engine
-                mean, var = eng.posterior(Xd)
-            scores = self._analytic_scores(eng, acqf, mean, var, self._sign(surrogate), alive)
-            val, idx = eng.argmax(scores)
-            if self.shard is not None:
-                val, idx, _ = self.shard.global_argmax(val, idx, Xd)
-            from baybe_amd.engine import GreedyResult
-
-            res = GreedyResult([int(idx)], [float(val)])
-        else:
-            res = surrogate.engine.greedy_qlogei(
-                Xd, batch_size, S=acqf.n_mc_samples, seed=self._sampler_seed(), sign=self._sign(surrogate),
-                X_pending=self._pending_comp, best_f=self._best_f, shard=self.shard, kind=acqf.kind,
-                beta=getattr(acqf, "beta", 0.2), alive=alive, **({} if self._program is None else {"objective": self._program}),
-            )
+        res = self._scorer.select(Xd, batch_size, seeds=self._sampler_seed, X_pending=self._pending_comp, alive=alive,
+                                  shard=self.shard)
         idxs = labels[np.asarray(res.indices, dtype=np.int64)]
         return (idxs, res) if return_values else idxs
 
@@ -886,7 +808,7 @@ class HipRecommenderImpl:
         _check_continuous_part(cont, self.continuous_optimizer)
         self._last_continuous_trace = []
         acqf, surrogate = self._acqf_in_use, self._surrogate_model
-        if self._nehvi is not None:
+        if not self._scorer.supports_continuous:
             raise IncompatibilityError("Multi-output objectives (qLogNEHVI / qNEHVI / qLogNParEGO) and qNEI / qLogNEI in hybrid / continuous spaces are not on the HIP path; use BotorchRecommender.")
         if batch_size > 1 and not acqf.supports_batching:
             raise IncompatibleAcquisitionFunctionError(
@@ -933,9 +855,9 @@ class HipRecommenderImpl:
         picks, pick_labels = [], []
         for _step in range(batch_size):
             pend = np.vstack([base] + picks) if picks else base
-            scores = self._mc_or_analytic(eng, acqf, X, mean, var, pend, seed, self._sign(surrogate))
+            scores = self._scorer.scores(X, mean, var, pend, seed)
             if gradient:
-                best_row = self._gradient_refine(eng, acqf, X, scores, Nd, R, dd, cb, pend, seed, self._sign(surrogate), poly)
+                best_row = self._gradient_refine(eng, acqf, X, scores, Nd, R, dd, cb, pend, seed, self._scorer.sign, poly)
                 picks.append(best_row.reshape(1, -1))
                 if has_disc:
                     pick_labels.append(labels[int(np.nonzero((D == best_row[:dd]).all(axis=1))[0][0])])
@@ -944,7 +866,7 @@ class HipRecommenderImpl:
             _, top = eng.topk(scores, k)
             top = [int(t) for t in top if t >= 0]
             starts = X[torch.as_tensor(top, device=X.device)].cpu().numpy()
-            best_row, _ = self._compass_refine(eng, acqf, starts, dd, cb, pend, seed, self._sign(surrogate), iters=min(96, 24 + 8 * dc))
+            best_row, _ = self._compass_refine(eng, starts, dd, cb, pend, seed, iters=min(96, 24 + 8 * dc))
             picks.append(best_row.reshape(1, -1))
             if has_disc:  # the label of the refined winner's discrete part (copied bit for bit from its start row)
                 pick_labels.append(labels[int(np.nonzero((D == best_row[:dd]).all(axis=1))[0][0])])
@@ -975,13 +897,6 @@ class HipRecommenderImpl:
                                            "use 'Random' or sampling_percentage=1.") from ex
             return list(farthest_point_sampling(Dcomp.to_numpy(), n_keep))
         raise ValueError(f"Unrecognized sampling method: '{name}'.")
-
-    def _mc_or_analytic(self, eng, acqf, X, mean, var, pend, seed, sign):
-        if acqf.is_analytic:
-            if len(pend):
-                raise IncompatibleAcquisitionFunctionError("Analytic acquisition functions score single points only.")
-            return self._analytic_scores(eng, acqf, mean, var, sign)
-        return self._mc_scores_with_pending(eng, acqf, X, mean, var, pend, seed, sign)
 
     def _gradient_refine(self, eng, acqf, X, scores, Nd: int, R: int, dd: int, cb: np.ndarray, pend, seed, sign, poly=None):
         """Gradient-based refinement of one greedy step.  Starts as the reference chooses them, per discrete row its ``n_restarts``
@@ -1036,7 +951,7 @@ class HipRecommenderImpl:
                                             "projections": project.calls if project is not None else 0})
         return final[i]
 
-    def _compass_refine(self, eng, acqf, starts: np.ndarray, dd: int, cb: np.ndarray, pend, seed, sign, iters: int = 24):
+    def _compass_refine(self, eng, starts: np.ndarray, dd: int, cb: np.ndarray, pend, seed, iters: int = 24):
         """Compass (pattern) search on the continuous coordinates of ``starts`` [k, d], all starts advancing together: per
         iteration 2 d_c probes per start (plus and minus the start's step along every continuous axis, clipped to the box) are
         scored in ONE device pass; a start moves to its best improving probe, otherwise its step halves.  Returns the best row and
@@ -1047,12 +962,12 @@ class HipRecommenderImpl:
         span = cb[1] - cb[0]
         if dc == 0:
             m, v = eng.posterior(cur)
-            val = self._mc_or_analytic(eng, acqf, cur, m, v, pend, seed, sign).cpu().numpy()
+            val = self._scorer.scores(cur, m, v, pend, seed).cpu().numpy()
             i = int(np.argmax(val))
             return cur[i], float(val[i])
         step = np.full(k, 0.125)  # fraction of the box, per start
         m, v = eng.posterior(cur)
-        val = self._mc_or_analytic(eng, acqf, cur, m, v, pend, seed, sign).cpu().numpy()
+        val = self._scorer.scores(cur, m, v, pend, seed).cpu().numpy()
         for _ in range(iters):
             probes = np.repeat(cur, 2 * dc, axis=0)  # [k * 2 dc, d]: start s, axis a, sign
             for a in range(dc):
@@ -1060,7 +975,7 @@ class HipRecommenderImpl:
                     rows = np.arange(k) * 2 * dc + 2 * a + off
                     probes[rows, dd + a] = np.clip(cur[:, dd + a] + sg * step * span[a], cb[0, a], cb[1, a])
             pm, pv = eng.posterior(probes)
-            pval = self._mc_or_analytic(eng, acqf, probes, pm, pv, pend, seed, sign).cpu().numpy().reshape(k, 2 * dc)
+            pval = self._scorer.scores(probes, pm, pv, pend, seed).cpu().numpy().reshape(k, 2 * dc)
             j = pval.argmax(axis=1)
             better = pval[np.arange(k), j] > val
             rows = np.arange(k) * 2 * dc + j
@@ -1072,124 +987,18 @@ class HipRecommenderImpl:
         i = int(np.argmax(val))
         return cur[i], float(val[i])
 
-    def _desirability_moments(self, X):
-        """(first engine, mean, var) of the Gaussian desirability N(sum_t c_t mu_t + offset, sum_t c_t^2 sigma_t^2) of an arithmetic
-        mean of affine targets (``DesirabilityProgram.as_affine``; to_botorch_posterior_transform, objectives/desirability.py:266-320)."""
-        c, offset = self._program.as_affine()
-        engines = [m.engine for m in self._surrogate_model.models]
-        mean = var = None
-        for ct, e in zip(c, engines):
-            m, v = e.posterior(X)
-            mean = ct * m + offset if mean is None else mean + ct * m
-            var = (ct * ct) * v if var is None else var + (ct * ct) * v
-        return engines[0], mean, var
-
-    def _analytic_scores(self, eng, acqf, mean, var, sign, alive=None):
-        if _is_desirability(self._program):  # (the moments are the desirability's already)
-            return eng.analytic_acq(acqf.kind, mean, var, self._best_f, 1.0, getattr(acqf, "beta", 0.2),
-                                    getattr(acqf, "maximize", True), alive)
-        if self._program is not None:
-            # an affine objective is the reference's posterior transform (objectives/single.py:77-91): N(a mu + b, a^2 sigma^2)
-            a, b = self._program.as_affine()
-            mean, var, sign = a * mean + b, (a * a) * var, 1.0
-        return eng.analytic_acq(acqf.kind, mean, var, self._best_f, sign, getattr(acqf, "beta", 0.2),
-                                getattr(acqf, "maximize", True), alive)
-
     # ---- read-backs (Campaign.acquisition_values / joint_acquisition_value) ---------------------
     def _joint_value(self, comp: np.ndarray) -> float:
-        """qLogEI of one q-batch (candidate = first row, the others enter as pending rows)."""
-        if getattr(self._surrogate_model, "is_independent_gaussian", False) and len(comp) != 1:
-            from baybe_amd.exceptions import IncompatibleSurrogateError
-            from baybe_amd.linear import JOINT_TEXT
-
-            raise IncompatibleSurrogateError(f"'{type(self._surrogate_model).__name__}' {JOINT_TEXT}.")
-        if _is_desirability(self._program):
-            if self._nehvi is None:  # analytic: single points only
-                if len(comp) != 1 or self._pending_comp is not None:
-                    raise IncompatibleAcquisitionFunctionError("Analytic acquisition functions score single points only.")
-                eng, mean, var = self._desirability_moments(comp)
-                return float(self._analytic_scores(eng, self._acqf_in_use, mean, var, 1.0).cpu().numpy()[0])
-            base = self._pending_comp if self._pending_comp is not None else np.zeros((0, comp.shape[1]))
-            sc = self._nehvi.score(comp[:1], X_pending=np.vstack([comp[1:], base]), seed=self._sampler_seed())
-            return float(sc.cpu().numpy()[0])
-        if _is_ehvi(self._acqf_in_use) or _is_nipv(self._acqf_in_use):  # one joint q-batch: the batch and the pending experiments
-            return self._nehvi.joint_value(comp, X_pending=self._pending_comp, seed=self._sampler_seed())
-        if self._nehvi is not None:
-            # incremental NEHVI: the batch value is the value of its last point given the others
-            self._nehvi.prepare(self._sampler_seed(), np.vstack([comp[:-1]] + ([self._pending_comp] if self._pending_comp is not None else [])) if len(comp) > 1 or self._pending_comp is not None else None)
-            sc = self._nehvi.score(self._nehvi.outputs[0].engine._as_dev(comp[-1:]))
-            return float(sc.cpu().numpy()[0])
-        surrogate = self._surrogate_model
-        eng = surrogate.engine
-        acqf = self._acqf_in_use
-        base = self._pending_comp if self._pending_comp is not None else np.zeros((0, comp.shape[1]))
-        pend = np.vstack([comp[1:], base])
-        seed = self._sampler_seed()
-        mean, var = eng.posterior(comp[:1])
-        if acqf.is_analytic:
-            if len(pend):
-                raise IncompatibleAcquisitionFunctionError("Analytic acquisition functions score single points only.")
-            return float(self._analytic_scores(eng, acqf, mean, var, self._sign(surrogate)).cpu().numpy()[0])
-        s = self._mc_scores_with_pending(eng, acqf, comp[:1], mean, var, pend, seed, self._sign(surrogate))
-        return float(s.cpu().numpy()[0])
-
-    def _mc_scores_with_pending(self, eng, acqf, comp, mean, var, pend, seed, sign):
-        """MC acquisition values of the t-batches [x_i ; pend] for the read-back APIs.  Up to 15 pending rows ride on the handle's
-        pending state; beyond that (qLogEI only, up to 63 - the same limit ``_check_batch_size`` admits for recommend()) the
-        columns come from ``cross_cov_many`` and the joint kernel takes the pending statistics explicitly, as in the greedy loop."""
-        beta = getattr(acqf, "beta", 0.2)
-        prog = self._program
-        okw = {} if prog is None else {"objective": prog}
-        if len(pend) == 0:
-            z = sobol_normal_base_samples(acqf.n_mc_samples, 1, seed)[:, 0]
-            return eng.mc_acq(acqf.kind, mean, var, z, self._best_f, sign, beta, **okw)
-        z = sobol_normal_base_samples(acqf.n_mc_samples, 1 + len(pend), seed)
-        if len(pend) > _lib.MAX_PENDING:
-            if prog is not None:
-                raise IncompatibilityError(
-                    f"{len(pend)} pending / batch rows exceed the largest joint q-batch of the HIP kernels for a transformed target "
-                    f"({_lib.MAX_PENDING + 1} points).")
-            if acqf.kind != "qLogEI" or len(pend) > _lib.MAX_PENDING_BIG:
-                raise IncompatibilityError(
-                    f"{len(pend)} pending / batch rows exceed the largest joint q-batch of the HIP kernels for '{type(acqf).__name__}' "
-                    f"({_lib.MAX_PENDING_BIG + 1} points for qLogEI, {_lib.MAX_PENDING + 1} otherwise).")
-            cross = eng.cross_cov_many(comp, pend)
-            s = eng.qlogei_pending_big(mean, var, cross, pend, z, self._best_f, sign)
-        else:
-            stats = eng.set_pending(pend)
-            cross = eng.cross_cov(comp)
-            if prog is not None:
-                okw["stats"] = stats
-            s = eng.mc_acq(acqf.kind, mean, var, z, self._best_f, sign, beta, cross=cross, **okw)
-        eng.set_pending(None)
-        return s
+        """The acquisition value of one q-batch, given the pending rows."""
+        return self._scorer.joint_value(comp, seeds=self._sampler_seed, X_pending=self._pending_comp)
 
     def acquisition_values(self, candidates: pd.DataFrame, searchspace, objective, measurements,
                            pending_experiments=None, acquisition_function=None) -> pd.Series:
         """``BayesianRecommender.acquisition_values`` (base.py:199-238): one value per candidate."""
-        surrogate, acqf = self._setup_acqf(searchspace, objective, measurements, pending_experiments, acquisition_function)
+        self._setup_acqf(searchspace, objective, measurements, pending_experiments, acquisition_function)
         comp = np.ascontiguousarray(searchspace.transform(candidates, allow_extra=True).to_numpy(dtype=np.float64))
-        if _is_desirability(self._program):
-            if self._nehvi is None:
-                eng, mean, var = self._desirability_moments(comp)
-                return pd.Series(self._analytic_scores(eng, acqf, mean, var, 1.0).cpu().numpy(), index=candidates.index)
-            sc = self._nehvi.score(comp, X_pending=self._pending_comp, seed=self._sampler_seed())
-            return pd.Series(sc.cpu().numpy(), index=candidates.index)
-        if _is_ehvi(acqf) or _is_nipv(acqf):
-            sc = self._nehvi.score(comp, X_pending=self._pending_comp, seed=self._sampler_seed())
-            return pd.Series(sc.cpu().numpy(), index=candidates.index)
-        if self._nehvi is not None:
-            self._nehvi.prepare(self._sampler_seed(), self._pending_comp)
-            sc = self._nehvi.score(self._nehvi.outputs[0].engine._as_dev(comp))
-            return pd.Series(sc.cpu().numpy(), index=candidates.index)
-        eng = surrogate.engine
-        mean, var = eng.posterior(comp)
-        if acqf.is_analytic:
-            s = self._analytic_scores(eng, acqf, mean, var, self._sign(surrogate))
-            return pd.Series(s.cpu().numpy(), index=candidates.index)
-        pend = self._pending_comp if self._pending_comp is not None else np.zeros((0, comp.shape[1]))
-        s = self._mc_scores_with_pending(eng, acqf, comp, mean, var, pend, self._sampler_seed(), self._sign(surrogate))
-        return pd.Series(s.cpu().numpy(), index=candidates.index)
+        scores = self._scorer.values(comp, seeds=self._sampler_seed, X_pending=self._pending_comp)
+        return pd.Series(scores.cpu().numpy(), index=candidates.index)
 
     def joint_acquisition_value(self, candidates: pd.DataFrame, searchspace, objective, measurements,
                                 pending_experiments=None, acquisition_function=None) -> float:
@@ -1282,7 +1091,7 @@ def recommender_fields(with_base_fields: bool = True, surrogate_factory=HipGauss
         "_best_f": field(default=None, init=False, eq=False, repr=False),
         "_pending_comp": field(default=None, init=False, eq=False, repr=False),
         "_cand_cache": field(default=None, init=False, eq=False, repr=False),
-        "_nehvi": field(default=None, init=False, eq=False, repr=False),
+        "_scorer": field(default=None, init=False, eq=False, repr=False),
         "_acqf_in_use": field(default=None, init=False, eq=False, repr=False),
         "_program": field(default=None, init=False, eq=False, repr=False),  # ObjectiveProgram of a transformed single target, or a DesirabilityProgram
         # per greedy step of the last hybrid / continuous recommendation under "gradient": starts, final points, values, projection calls (tests, timing)

@@ -46,7 +46,7 @@ def call(m, label, prof=False):
         print("own_us   cum_us  calls  function")
         for tt, ct, nc, name in rows:
             print(f"{tt * 1e6:7.0f} {ct * 1e6:8.0f} {nc:6d}  {name}")
-        nv = rec._nehvi
+        nv = rec._scorer
         if nv is not None:
             print("last prune parts", getattr(nv, "last_prune_ms", None), "last set-up", nv.last_setup_ms)
     return got

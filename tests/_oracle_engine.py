@@ -25,6 +25,7 @@ from _problems import oracle_params, oracle_spec
 from baybe_amd import engine as engine_mod
 from baybe_amd import gp_spec
 from baybe_amd.engine import GreedyResult, HipGP, ModelFittingError
+from baybe_amd.nehvi import HipNEHVI
 from oracle import gp_oracle as go
 
 
@@ -325,6 +326,10 @@ class OracleNEHVI:
             alive[idx] = 0
             picks.append(X_dev[idx, :d].numpy().reshape(1, d))
         return GreedyResult(indices, values)
+
+    # the recommender's surface is the PRODUCT's (baybe_amd.scoring): the seeds a path draws, and their order, are under test
+    supports_continuous, check_request = HipNEHVI.supports_continuous, staticmethod(HipNEHVI.check_request)
+    select, values, joint_value, _prepare_drawing = HipNEHVI.select, HipNEHVI.values, HipNEHVI.joint_value, HipNEHVI._prepare_drawing
 
 
 def install(monkeypatch):

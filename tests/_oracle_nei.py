@@ -10,6 +10,7 @@ import torch
 import _nei_reference as ref
 from baybe_amd import engine as engine_mod
 from baybe_amd.engine import GreedyResult
+from baybe_amd.nehvi import HipNEHVI
 
 
 class OracleNEI:
@@ -53,6 +54,10 @@ class OracleNEI:
             alive[idx] = 0
             picks.append(X_dev[idx, :d].numpy().reshape(1, d))
         return GreedyResult(indices, values)
+
+    # the recommender's surface is the PRODUCT's (baybe_amd.scoring): the seeds a path draws, and their order, are under test
+    supports_continuous, check_request = HipNEHVI.supports_continuous, staticmethod(HipNEHVI.check_request)
+    select, values, joint_value, _prepare_drawing = HipNEHVI.select, HipNEHVI.values, HipNEHVI.joint_value, HipNEHVI._prepare_drawing
 
 
 def install(monkeypatch):

@@ -162,6 +162,30 @@ def test_a_fitted_recommender_and_its_copy_recommend_the_same(how):
     assert len(rec._surrogate_model._engine._X_train) == 20 and len(twin._surrogate_model._engine._X_train) == 23
 
 
+@pytest.mark.parametrize("how", ["deepcopy", "pickle"])
+def test_a_single_target_recommender_drops_its_scorer_on_copy(how):
+    """The single-target paths keep a scorer in the slot too (it wraps the fitted engine): a copy starts without one, builds its
+    own on the next call, and the original keeps its."""
+    import torch
+
+    from baybe_amd.recommenders import HipBotorchRecommender
+
+    space = _space()
+    obj = SingleTargetObjective(NumericalTarget("yield"))
+    meas = _measured(space, 20, 1)
+    rec = HipBotorchRecommender()
+    torch.manual_seed(3)
+    first = rec.recommend(2, space, obj, meas)
+    kept = rec._scorer
+    assert type(kept).__name__ == "HipSingleTargetAcq" and kept.engine is rec._surrogate_model._engine
+    twin = copy.deepcopy(rec) if how == "deepcopy" else pickle.loads(pickle.dumps(rec))
+    assert twin._scorer is None and rec._scorer is kept
+    torch.manual_seed(3)
+    copied = twin.recommend(2, space, obj, meas)
+    assert list(copied.index) == list(first.index)
+    assert twin._scorer is not None and twin._scorer.engine is twin._surrogate_model._engine is not kept.engine
+
+
 def test_pareto_recommender_copies():
     import torch
 
@@ -176,7 +200,7 @@ def test_pareto_recommender_copies():
     torch.manual_seed(11)
     a = rec.recommend(2, space, obj, meas)
     twin = copy.deepcopy(rec)
-    assert twin._nehvi is None and len(twin._surrogate_model._models) == 2
+    assert twin._scorer is None and len(twin._surrogate_model._models) == 2
     torch.manual_seed(11)
     b = twin.recommend(2, space, obj, meas)
     assert list(a.index) == list(b.index)

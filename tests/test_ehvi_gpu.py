@@ -231,7 +231,7 @@ def test_recommender_end_to_end(m, pending):
         assert all(g > 100 * ec.gap_tolerance(log, v) for v, g in zip(vals, gaps)), (name, vals, gaps)
         assert got.index.tolist() == exp.index[idx].tolist(), name
         lo, up = oe.model_cells(models, signs, X_all, ref)
-        glo, gup = rec._nehvi.cells()
+        glo, gup = rec._scorer.cells()
         assert glo.shape == lo.shape and np.allclose(np.sort(glo, axis=0), np.sort(lo, axis=0), atol=1e-9)
         seed = ec.next_sampler_seed(5)
         acq = rec.acquisition_values(exp.iloc[:60], space, objective, meas, pending_experiments=pend_df).to_numpy()

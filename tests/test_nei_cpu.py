@@ -114,7 +114,7 @@ def test_recommend_through_the_plugin_classes(monkeypatch):
     rec = HipBotorchRecommender(acquisition_function="qLogNEI")
     torch.manual_seed(17)
     got = rec.recommend(3, space, obj, meas, pending_experiments=pending)
-    assert type(rec._nehvi).__name__ == "OracleNEI" and rec._best_f is None
+    assert type(rec._scorer).__name__ == "OracleNEI" and rec._best_f is None
     torch.manual_seed(17)
     seed, pseed = draw_sampler_seed(), draw_sampler_seed()
     model = rec._surrogate_model.engine._model
@@ -123,7 +123,7 @@ def test_recommend_through_the_plugin_classes(monkeypatch):
     comp = space.discrete.comp_rep.to_numpy(dtype=np.float64)
     picks, _ = ref.greedy(model, 1.0, Xb[keep], comp, 3, 512, seed, X_pending=space.transform(pending).to_numpy(dtype=np.float64))
     assert list(got.index) == list(exp.index[picks])
-    assert np.array_equal(rec._nehvi._pruned, Xb[keep])
+    assert np.array_equal(rec._scorer._pruned, Xb[keep])
     small = HipBotorchRecommender(acquisition_function=type("qNoisyExpectedImprovement", (), {"prune_baseline": False})())
     many = small.recommend(20, space, obj, meas)  # no joint q' kernel, so no 16 / 64-point cap
     assert len(set(many.index)) == 20 and small._acqf_in_use.kind == "qNEI" and small._acqf_in_use.prune_baseline is False

@@ -290,7 +290,7 @@ def test_recommend_through_the_plugin_surface():
     rec = HipBotorchRecommender(acquisition_function="qLogNEI")
     torch.manual_seed(31)
     got = rec.recommend(2, space, obj, meas)
-    assert type(rec._nehvi).__name__ == "HipNEI" and rec._nehvi.last_form == "fused"
+    assert type(rec._scorer).__name__ == "HipNEI" and rec._scorer.last_form == "fused"
     eng = rec._surrogate_model.engine
     model = go.GPModel(oracle_spec(eng.spec), oracle_params(eng.spec, eng.params), eng._X_train, eng._y_train)
     torch.manual_seed(31)

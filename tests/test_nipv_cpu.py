@@ -226,8 +226,8 @@ def test_recommender_field_and_plugin_fields():
     import copy
 
     rec = R(nipv="device", acquisition_function="qNIPV")
-    rec._nehvi = object()
-    assert copy.deepcopy(rec)._nehvi is None and copy.deepcopy(rec).nipv == "device"  # per-call state is dropped on copy
+    rec._scorer = object()
+    assert copy.deepcopy(rec)._scorer is None and copy.deepcopy(rec).nipv == "device"  # per-call state is dropped on copy
 
 
 # ---- refusals, before anything is fitted -----------------------------------------------------------------------------------------------

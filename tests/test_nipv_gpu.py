@@ -230,7 +230,7 @@ def test_recommender_end_to_end():
         np.random.seed(5)  # (the tie-breaks of farthest point sampling on a grid)
         got = rec.recommend(nc.CAMPAIGN_BATCH, space, objective, meas, pending_experiments=pend_df)
         batches.append(got.index.tolist())
-        P = rec._nehvi.P
+        P = rec._scorer.P
         assert P.shape == (nc.CAMPAIGN_POINTS, 3)
         prm = rec._surrogate_model.engine.params
         om = go.GPModel(go.GPSpec.baybe_default(3, np.zeros(3), np.ones(3)), go.GPParams(prm.lengthscale, prm.noise, prm.mean), X_all,
@@ -241,13 +241,13 @@ def test_recommender_end_to_end():
         assert got.index.tolist() == exp.index[[st.index for st in steps]].tolist()
         np.random.seed(6)
         acq = rec.acquisition_values(exp.iloc[:60], space, objective, meas, pending_experiments=pend_df).to_numpy()
-        P = rec._nehvi.P
+        P = rec._scorer.P
         a, s = on.direct(om, Xc[:60], Xc[[100]], P), on.schur(om, Xc[:60], Xc[[100]], P)
         dev = np.abs(acq - a.value) - nc.C_BOUND * s.tol / len(P)
         assert dev.max() <= VAR_TOL * om.ysd**2, dev.max()
         np.random.seed(7)
         jv = rec.joint_acquisition_value(exp.iloc[[3, 140, 77]], space, objective, meas, pending_experiments=pend_df)
-        P = rec._nehvi.P
+        P = rec._scorer.P
         rest = Xc[[140, 77, 100]]
         aj, sj = on.direct(om, Xc[[3]], rest, P), on.schur(om, Xc[[3]], rest, P)
         assert abs(jv - aj.value[0]) <= nc.C_BOUND * sj.tol[0] / len(P) + VAR_TOL * om.ysd**2, (jv, aj.value[0])

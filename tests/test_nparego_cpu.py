@@ -211,11 +211,11 @@ def test_recommend_through_the_plugin_classes(monkeypatch):
     rec = HipBotorchRecommender(acquisition_function="qLogNParEGO")
     torch.manual_seed(17)
     got = rec.recommend(3, space, obj, meas, pending_experiments=pending)
-    assert type(rec._nehvi).__name__ == "OracleNParEGO" and rec._best_f is None
+    assert type(rec._scorer).__name__ == "OracleNParEGO" and rec._best_f is None
     torch.manual_seed(17)
     w = ref.sample_simplex(2)
     seed, pseed = draw_sampler_seed(), draw_sampler_seed()
-    assert np.array_equal(rec._nehvi.weights, w) and (w >= 0).all() and abs(w.sum() - 1) < 1e-15
+    assert np.array_equal(rec._scorer.weights, w) and (w >= 0).all() and abs(w.sum() - 1) < 1e-15
     models = [m.engine._model for m in rec._surrogate_model.models]
     signs = np.array([1.0, -1.0])
     Xb = space.transform(meas, allow_extra=True).to_numpy(dtype=np.float64)
@@ -224,14 +224,14 @@ def test_recommend_through_the_plugin_classes(monkeypatch):
     comp = space.discrete.comp_rep.to_numpy(dtype=np.float64)
     picks, _ = ref.greedy(models, signs, Xb[keep], comp, 3, 512, seed, w, lo, hi, X_pending=space.transform(pending).to_numpy(dtype=np.float64))
     assert list(got.index) == list(exp.index[picks])
-    assert np.array_equal(rec._nehvi._pruned, Xb[keep])
+    assert np.array_equal(rec._scorer._pruned, Xb[keep])
     # the read-backs go through the same prepare / score surface
     acq = rec.acquisition_values(exp.iloc[:5], space, obj, meas)
     assert np.isfinite(acq.to_numpy()).all()
 
     given = HipBotorchRecommender(acquisition_function=A.qLogNParEGO(prune_baseline=False, n_mc_samples=32))
     many = given.recommend(20, space, obj, meas)  # no joint q' kernel, so no 16 / 64-point cap
-    assert len(set(many.index)) == 20 and given._acqf_in_use.kind == "qLogNParEGO" and len(given._nehvi._pruned) == len(meas)
+    assert len(set(many.index)) == 20 and given._acqf_in_use.kind == "qLogNParEGO" and len(given._scorer._pruned) == len(meas)
 
     calls = []
 
@@ -244,7 +244,7 @@ def test_recommend_through_the_plugin_classes(monkeypatch):
                                     shard=SimpleNamespace(world=1, rank=0, N_total=n, start=0, stop=n, agree=agree))
     torch.manual_seed(17)
     sharded.recommend(1, space, obj, meas)
-    assert np.array_equal(sharded._nehvi.weights, [0.25, 0.75])
+    assert np.array_equal(sharded._scorer.weights, [0.25, 0.75])
     assert isinstance(calls[0], np.ndarray) and np.array_equal(calls[0], w)  # rank 0's draw goes in first, before the two seeds
     assert calls[1:] == [seed, pseed]
 
@@ -255,7 +255,7 @@ def test_recommend_through_the_plugin_classes(monkeypatch):
     explicit.recommend(1, space, obj, meas)
     torch.manual_seed(17)
     assert calls == [draw_sampler_seed(), draw_sampler_seed()]  # given weights consume nothing from the generator
-    assert np.array_equal(explicit._nehvi.weights, [0.3, 0.7]) and explicit._nehvi.S == 32
+    assert np.array_equal(explicit._scorer.weights, [0.3, 0.7]) and explicit._scorer.S == 32
 
 
 def test_plain_qnehvi_through_the_plugin_classes(monkeypatch):
@@ -271,21 +271,21 @@ def test_plain_qnehvi_through_the_plugin_classes(monkeypatch):
     rec = HipBotorchRecommender(acquisition_function=A.qNEHVI(n_mc_samples=16))
     torch.manual_seed(23)
     got = rec.recommend(2, space, obj, meas)
-    assert type(rec._nehvi).__name__ == "OracleNEHVIPlain"
+    assert type(rec._scorer).__name__ == "OracleNEHVIPlain"
     torch.manual_seed(23)
     seed, pseed = draw_sampler_seed(), draw_sampler_seed()
     models = [m.engine._model for m in rec._surrogate_model.models]
     signs = np.array([1.0, -1.0])
     Xb = space.transform(meas, allow_extra=True).to_numpy(dtype=np.float64)
     ref_point = no.compute_ref_point(meas[["t1", "t2"]].to_numpy() * signs[None, :])
-    assert np.allclose(rec._nehvi.ref, ref_point, rtol=1e-15, atol=0)
+    assert np.allclose(rec._scorer.ref, ref_point, rtol=1e-15, atol=0)
     keep = no.prune_baseline(models, signs, Xb, ref_point, pseed)
     comp = space.discrete.comp_rep.to_numpy(dtype=np.float64)
     picks, vals = ref.qnehvi_greedy(models, signs, Xb[keep], ref_point, comp, 2, 16, seed)
     assert list(got.index) == list(exp.index[picks]) and vals[0] > 0
     log = HipBotorchRecommender()  # the default for a Pareto objective is still qLogNEHVI with today's arguments
     log.recommend(1, space, obj, meas)
-    assert type(log._nehvi).__name__ == "OracleNEHVI" and log._nehvi.S == 128
+    assert type(log._scorer).__name__ == "OracleNEHVI" and log._scorer.S == 128
 
 
 def test_single_target_objective_is_refused(monkeypatch):

@@ -288,11 +288,11 @@ def test_recommend_through_the_plugin_surface():
     rec = HipBotorchRecommender(acquisition_function="qLogNParEGO")
     torch.manual_seed(31)
     got = rec.recommend(2, space, obj, meas)
-    assert type(rec._nehvi).__name__ == "HipNParEGO"
+    assert type(rec._scorer).__name__ == "HipNParEGO"
     torch.manual_seed(31)
     w = ref.sample_simplex(2)
     seed, pseed = draw_sampler_seed(), draw_sampler_seed()
-    assert np.array_equal(rec._nehvi.weights, w)
+    assert np.array_equal(rec._scorer.weights, w)
     models = []
     for sub in rec._surrogate_model.models:
         eng = sub.engine

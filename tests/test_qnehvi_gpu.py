@@ -148,7 +148,7 @@ def test_recommend_through_the_plugin_surface():
     rec = HipBotorchRecommender(acquisition_function=A.qNEHVI(n_mc_samples=32))
     torch.manual_seed(31)
     got = rec.recommend(2, space, obj, meas)
-    assert type(rec._nehvi).__name__ == "HipNEHVIPlain"
+    assert type(rec._scorer).__name__ == "HipNEHVIPlain"
     torch.manual_seed(31)
     seed, pseed = draw_sampler_seed(), draw_sampler_seed()
     models = []
